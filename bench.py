@@ -22,7 +22,14 @@ blobs, ids offset by rank; C3 is a fixed total split by LPT).  A gloo barrier
 brackets the timed region, the time is the max over ranks, and value = units
 processed by all ranks / that time.
 
-cpu_baseline (rank 0, N=1): the CPU restatement of the reference's path
+A plain run sets up, warms up, times --steps steps and prints the line (metric, value,
+ms_per_step and the kernels' launch times of those steps).  --full adds every other leg
+after the timed steps: the CPU baseline, the host-offload, end-to-end and back-to-back
+legs, the sweeps, the live SHA issue ceiling and the checks against the oracle (each still
+under its own --no-* switch).  --dump-outputs DIR writes the last timed step's outputs as
+DIR/<name>.npy (dump_outputs).
+
+cpu_baseline (--full; rank 0, N=1): the CPU restatement of the reference's path
 (oracle/: the two-pass SHA-NI + PCLMUL run, or the HRW ring placement) on the
 host cores of this box, on a bounded sample of the same synthetic inputs.
 """
@@ -113,7 +120,8 @@ WORKLOADS = {
                                          "GetPieceSum, split between host threads and the GPU; 1 in 64 corrupted"),
     "c4": dict(kind="pieces", steps=20, warmup=2,  # 3.6 ms steps
                desc="C4: one 20 GiB blob per GPU, 256 KiB pieces (81,920), piece sums only"),
-    "c3": dict(kind="chunked", desc="C3: 20k blobs of 100 MiB + (rng mod 968,884,225) B, 4 MiB pieces, "
+    "c3": dict(kind="chunked", steps=1, warmup=0,  # a step = the whole shard, ~20 s at N=8
+               desc="C3: 20k blobs of 100 MiB + (rng mod 968,884,225) B, 4 MiB pieces, "
                                     "LPT-sharded by blob, streamed through HBM in windows"),
     "engine": dict(kind="engine", steps=3, warmup=1,
                    desc="256 concurrent GPU Digesters (core.Digester per upload / cache fill, "
@@ -333,6 +341,29 @@ class Timer:
         return float(t.item())
 
 
+DUMP_MAX_BYTES = 60_000_000  # under 64 MB with the .npy headers
+
+
+def dump_outputs(a, rank, arrays):
+    """--dump-outputs DIR: the arrays the last timed step handed its caller, written right
+    after the timed region as DIR/<name>.npy (rank r > 0: <name>.rank<r>.npy).  Integers of
+    up to 16 bits (bytes, verdicts) go out as float32, wider ones (CRC-32 sums, owner
+    indices) as float64: both exact.  The inputs are synthetic and seeded, so two builds run
+    with the same arguments write comparable files.  All files together stay under 64 MB:
+    an array over its share is cut to a fixed seeded sample of its rows."""
+    if not a.dump_outputs:
+        return
+    os.makedirs(a.dump_outputs, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(1, len(arrays))
+    for name, x in arrays.items():
+        x = np.asarray(x)
+        ft = np.dtype(np.float32 if x.dtype.itemsize <= 2 else np.float64)
+        row = max(1, x.size // max(1, len(x))) * ft.itemsize
+        if len(x) * row > share:
+            x = x[np.sort(np.random.default_rng(0xD0).choice(len(x), share // row, replace=False))]
+        np.save(os.path.join(a.dump_outputs, name + (f".rank{rank}" if rank else "") + ".npy"), x.astype(ft))
+
+
 TRAFFIC_SOURCE = ("rocprofv3 FETCH_SIZE / WRITE_SIZE passes of this workload committed under profiles/ "
                   "(tools/pmc_traffic.py): NOT measured in this run (counters need their own profiler process)")
 VALU_NOTE = "rocprofv3 PMC passes committed under profiles/ (tools/pmc_valu.py): NOT measured in this run"
@@ -451,6 +482,7 @@ def run_metainfo(a, D, T, rank, world, res):
         t1 = time.perf_counter()
         crc_n, crc_ms = D.KernelTimer.stats("crc32_pieces")
         sha_n, sha_ms = D.KernelTimer.stats("sha256_multi")
+    dump_outputs(a, rank, {"piece_sums": sums_h[:arena.total_pieces], "digests": dg_h[:32 * n].reshape(n, 32)})
     elapsed = T.timed_region(t1 - t0)
     bytes_rank = int(sum(lens))
     value = world * bytes_rank * a.steps / elapsed / 1e9
@@ -586,6 +618,9 @@ def run_regen(a, D, T, rank, world, res):
         crc_n, crc_ms = D.KernelTimer.stats("crc32_pieces")
     if "ih" in raw:
         ihs[:] = [core.InfoHash(bytes(r)) for r in raw["ih"]]
+    if a.dump_outputs:
+        dump_outputs(a, rank, {"piece_sums": pin_s.a[:arena.total_pieces],
+                               "info_hashes": np.array([list(bytes(h)) for h in ihs], np.uint8).reshape(n, 20)})
     elapsed = T.timed_region(t1 - t0)
     bytes_rank = int(sum(lens))
     crc_avg = crc_ms / max(crc_n, 1)
@@ -607,7 +642,7 @@ def run_regen(a, D, T, rank, world, res):
                                    "groups); achieved = bytes per launch / average launch time; traffic = the "
                                    "single-launch PMC pass's bytes / launches per step")
     # spot-check the InfoHashes of the first blobs against the oracle's independent bencode + SHA-1
-    if rank == 0:
+    if rank == 0 and a.full:
         from oracle import oracle as O  # the checker (test infrastructure)
         O.build()
         ok = True
@@ -672,6 +707,7 @@ def run_verify(a, D, T, rank, world, res):
         T.barrier()
         t1 = time.perf_counter()
         crc_n, crc_ms = D.KernelTimer.stats("crc32_pieces")
+    dump_outputs(a, rank, {"verdicts": np.asarray(got[0], dtype=bool)})
     elapsed = T.timed_region(t1 - t0)
     bytes_rank = n * P
     rates = D.planner_rates()
@@ -707,21 +743,8 @@ def run_verify(a, D, T, rank, world, res):
                 "verdicts_match": bool(np.array_equal(got[0], want))})
     if world == 1 and not a.no_cpu_baseline:
         res["same_buffer"] = same_buffer_ab(step, [host.ctypes.data + i * P for i in range(n)], [P] * n, expected)
-    # the same pieces from pageable memory
-    pg = np.empty(n * P, dtype=np.uint8)
-    pg[:] = host
-    pdatas = [pg[i * P:(i + 1) * P] for i in range(n)]
-    pv = agentstorage.verify_pieces(pdatas, exp)
-    T.barrier()
-    t0 = time.perf_counter()
-    for _ in range(a.steps):
-        pv = agentstorage.verify_pieces(pdatas, exp)
-    T.barrier()
-    el = T.max_over_ranks(time.perf_counter() - t0)
-    res["pageable"] = {"value": round(world * bytes_rank * a.steps / el / 1e9, 3), "unit": "GB/s",
-                       "verdicts_match": bool(np.array_equal(pv, want)),
-                       "what": "the same batch from pageable host memory (numpy)"}
-    del pg, pdatas
+    if a.full:
+        res["pageable"] = verify_pageable(a, T, host, n, P, exp, want, world)
     if rank == 0 and not a.no_cpu_baseline:
         # 512 pieces = 2 GiB of distinct bytes: a sample of a few hundred MiB would sit in the
         # host's last-level cache across the repeated passes and overstate the CPU rate
@@ -735,6 +758,24 @@ def run_verify(a, D, T, rank, world, res):
             res["cpu_baseline"] = same_buffer_baseline(res["same_buffer"], n, P, "pinned receive pieces")
         else:
             res["cpu_baseline"] = cb
+
+
+def verify_pageable(a, T, host, n, P, exp, want, world):
+    """run_verify's batch again from pageable host memory (numpy)."""
+    from kraken_amd import agentstorage
+    pg = np.empty(n * P, dtype=np.uint8)
+    pg[:] = host
+    pdatas = [pg[i * P:(i + 1) * P] for i in range(n)]
+    pv = agentstorage.verify_pieces(pdatas, exp)
+    T.barrier()
+    t0 = time.perf_counter()
+    for _ in range(a.steps):
+        pv = agentstorage.verify_pieces(pdatas, exp)
+    T.barrier()
+    el = T.max_over_ranks(time.perf_counter() - t0)
+    return {"value": round(world * n * P * a.steps / el / 1e9, 3), "unit": "GB/s",
+            "verdicts_match": bool(np.array_equal(pv, want)),
+            "what": "the same batch from pageable host memory (numpy)"}
 
 
 def host_mem_budget():
@@ -1260,12 +1301,14 @@ def run_pieces(a, D, T, rank, world, res):
         crc_n, crc_ms = D.KernelTimer.stats("crc32_pieces")
     sums_h = pins[(a.steps - 1) & 1].a if a.steps else sums_h
     want = sums_h.copy()
-    T.barrier()
-    t2 = time.perf_counter()
-    run(a.steps, False)
-    T.barrier()
-    el_b2b = T.max_over_ranks(time.perf_counter() - t2)
-    same = all(np.array_equal(p.a, want) for p in pins)
+    dump_outputs(a, rank, {"piece_sums": want[:arena.total_pieces]})
+    if a.full:
+        T.barrier()
+        t2 = time.perf_counter()
+        run(a.steps, False)
+        T.barrier()
+        el_b2b = T.max_over_ranks(time.perf_counter() - t2)
+        same = all(np.array_equal(p.a, want) for p in pins)
     for st in streams:
         D.lib.krk_stream_destroy(st)
     elapsed = T.timed_region(t1 - t0)
@@ -1279,18 +1322,20 @@ def run_pieces(a, D, T, rank, world, res):
                 "config": {"workload": WORKLOADS[a.workload]["desc"], "bytes_per_gpu": bytes_rank,
                            "piece_length": P, "pieces_per_gpu": arena.total_pieces, "mode": "device-resident",
                            "steps": "serial (each step's sums on the host before the next is enqueued)"},
-                "back_to_back": {"value": round(world * bytes_rank * a.steps / el_b2b / 1e9, 3), "unit": "GB/s",
-                                 "ms_per_step": round(el_b2b / a.steps * 1e3, 3), "sums_match_serial": same,
-                                 "what": "the same steps with step k+1 enqueued while step k runs (two streams, "
-                                         "two sums buffers, every step's sums in pinned host memory)"},
+                **({"back_to_back": {"value": round(world * bytes_rank * a.steps / el_b2b / 1e9, 3), "unit": "GB/s",
+                                     "ms_per_step": round(el_b2b / a.steps * 1e3, 3), "sums_match_serial": same,
+                                     "what": "the same steps with step k+1 enqueued while step k runs (two streams, "
+                                             "two sums buffers, every step's sums in pinned host memory)"}}
+                   if a.full else {}),
                 "roofline": roofline_obj("crc32_pieces", crc_gbps, crc_avg, bytes_rank,
                                          load_traffic(a.pmc_json, a.workload, len(lens)).get("crc32_pieces")),
                 "kernels": {"crc32_pieces": {"launches": crc_n, "avg_ms": round(crc_avg, 3)}}})
     # InfoHash over the 81,920 sums stays on the host (bencode + SHA-1, core/metainfo.go:37-44)
-    from kraken_amd import core
-    t0 = time.perf_counter()
-    core._info_hash(P, sums_h[:arena.total_pieces], "0" * 64, lens[0])
-    res["info_hash_host_ms"] = round((time.perf_counter() - t0) * 1e3, 3)
+    if a.full:
+        from kraken_amd import core
+        t0 = time.perf_counter()
+        core._info_hash(P, sums_h[:arena.total_pieces], "0" * 64, lens[0])
+        res["info_hash_host_ms"] = round((time.perf_counter() - t0) * 1e3, 3)
     if a.workload == "c4" and not a.no_e2e:
         res["end_to_end"] = c4_end_to_end(D, T, arena, sums_h, P, world, ab=world == 1 and not a.no_cpu_baseline)
     if rank == 0 and not a.no_cpu_baseline:
@@ -1334,22 +1379,31 @@ def run_chunked(a, D, T, rank, world, res):
         return
     wr = WindowedRun(D, ids, lens, P, a.window_gib << 30,
                      cap=n if a.no_admission else (a.live_cap or None))
-    T.barrier()
-    with D.KernelTimer():
-        t0 = time.perf_counter()
+    # a step = one pass over the whole shard; every pass starts from fresh midstates and
+    # zeroed sums (a new ChunkedBatch, made outside the timed region like the first)
+    for _ in range(a.warmup):
         wr.run()
-        T.barrier()
-        t1 = time.perf_counter()
+        wr.cb = D.ChunkedBatch(lens, P)
+    secs = 0.0
+    with D.KernelTimer():
+        for k in range(a.steps):
+            if k:
+                wr.cb = D.ChunkedBatch(lens, P)
+            T.barrier()
+            t0 = time.perf_counter()
+            wr.run()
+            T.barrier()
+            secs += time.perf_counter() - t0
         sha_n, sha_ms = D.KernelTimer.stats("sha256_multi")
         crc_n, crc_ms = D.KernelTimer.stats("crc32_pieces")
         gen_n, gen_ms = D.KernelTimer.stats("synth_fill")
-    elapsed = T.timed_region(t1 - t0)
+    elapsed = T.timed_region(secs)
     bytes_rank = int(sum(lens))
     total_bytes = int(sum(c3_lengths(a.blobs or 20000)))
     cb = wr.cb
     res.update({"metric": "metainfo+digest GB/s (C3, device-generated windows)",
-                "value": round(total_bytes / elapsed / 1e9, 3), "unit": "GB/s", "steps": 1,
-                "ms_per_step": round(elapsed * 1e3, 3), "higher_is_better": True, "scaling": "strong",
+                "value": round(total_bytes * a.steps / elapsed / 1e9, 3), "unit": "GB/s", "steps": a.steps,
+                "ms_per_step": round(elapsed / a.steps * 1e3, 3), "higher_is_better": True, "scaling": "strong",
                 "dtype": "u8", "data": "synthetic (generated on the device per window, inside the timed region)",
                 "config": {"workload": WORKLOADS["c3"]["desc"], "blobs_total": a.blobs or 20000,
                            "blobs_this_rank": n, "bytes_this_rank": bytes_rank, "bytes_total": total_bytes,
@@ -1368,8 +1422,8 @@ def run_chunked(a, D, T, rank, world, res):
                         "rate) at any GPU count"})
     # Dominant kernel by device time: SHA-256 over every window (bytes / summed launch time).
     if sha_n:
-        gbps = bytes_rank / (sha_ms / 1e3) / 1e9
-        roof = roofline_obj("sha256_multi", gbps, sha_ms / sha_n, bytes_rank / sha_n, None)
+        gbps = bytes_rank * a.steps / (sha_ms / 1e3) / 1e9
+        roof = roofline_obj("sha256_multi", gbps, sha_ms / sha_n, bytes_rank * a.steps / sha_n, None)
         roof["chain"] = {"peak": None, "frac": None}
         # The chain bound: no schedule finishes before the longest blob's chain, which runs
         # at the per-stream ISA ceiling of the plan the first (largest) window takes.
@@ -1397,9 +1451,10 @@ def run_chunked(a, D, T, rank, world, res):
         res["roofline"] = roof
     dg = cb.digests.to_host(np.uint8, 32 * n).reshape(-1, 32)
     sums = cb.sums.to_host(np.uint32, max(cb.total_pieces, 1))
+    dump_outputs(a, rank, {"piece_sums": sums[:cb.total_pieces], "digests": dg})
     if rank == 0 and not a.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline_c3(ids, lens, P, dg, sums, cb.sums_off)
-    if rank == 0:  # spot-check three blobs against the one-shot device path
+    if rank == 0 and a.full:  # spot-check three blobs against the one-shot device path
         pick = sorted({0, n // 2, n - 1})
         wr.close()
         arena = D.BlobArena([lens[i] for i in pick], P, blob_ids=[ids[i] for i in pick])
@@ -1618,12 +1673,14 @@ def run_hrw(a, D, T, rank, world, res):
     enqueue_us = enq_s[0] / max(a.steps, 1) * 1e6
     locs_h = outs[(a.steps - 1) & 1][2].a if a.steps else locs_h
     want_locs = locs_h.copy()
-    T.barrier()
-    t2 = time.perf_counter()
-    run(a.steps, False)
-    T.barrier()
-    el_b2b = T.max_over_ranks(time.perf_counter() - t2)
-    b2b_ok = all(np.array_equal(outs[i][2].a, want_locs) for i in range(min(2, a.steps)))
+    if a.full:
+        T.barrier()
+        t2 = time.perf_counter()
+        run(a.steps, False)
+        T.barrier()
+        el_b2b = T.max_over_ranks(time.perf_counter() - t2)
+        b2b_ok = all(np.array_equal(outs[i][2].a, want_locs) for i in range(min(2, a.steps)))
+    mapped_locs = None
     try:
         # The same steps with locs in page-locked host memory: the gather writes the owner lists
         # over PCIe as it goes and the step has no copy-back (counts stay in HBM, as in the copy
@@ -1643,19 +1700,22 @@ def run_hrw(a, D, T, rank, world, res):
             t4 = time.perf_counter()
             mg_n, mg_ms = D.KernelTimer.stats("hrw_gather")
         el_m = T.max_over_ranks(t4 - t3)
-        m_ok = bool(np.array_equal(mouts[(a.steps - 1) & 1][0].a, want_locs)) if a.steps else True
-        T.barrier()
-        t5 = time.perf_counter()
-        run(a.steps, False, enqueue_mapped)
-        T.barrier()
-        el_mb = T.max_over_ranks(time.perf_counter() - t5)
-        m_ok = m_ok and all(np.array_equal(mouts[i][0].a, want_locs) for i in range(min(2, a.steps)))
+        mapped_locs = mouts[(a.steps - 1) & 1][0].a.copy()
+        m_ok = bool(np.array_equal(mapped_locs, want_locs))
+        b2b_m = {}
+        if a.full:
+            T.barrier()
+            t5 = time.perf_counter()
+            run(a.steps, False, enqueue_mapped)
+            T.barrier()
+            el_mb = T.max_over_ranks(time.perf_counter() - t5)
+            m_ok = m_ok and all(np.array_equal(mouts[i][0].a, want_locs) for i in range(min(2, a.steps)))
+            b2b_m = {"back_to_back": {"value": round(world * n * a.steps / el_mb, 1),
+                                      "ms_per_step": round(el_mb / a.steps * 1e3, 3)}}
         mg_avg = mg_ms / max(mg_n, 1)
         out_bytes = n * isz * R
         mapped = {"value": round(world * n * a.steps / el_m, 1), "unit": "digests/s",
-                  "ms_per_step": round(el_m / a.steps * 1e3, 3),
-                  "back_to_back": {"value": round(world * n * a.steps / el_mb, 1),
-                                   "ms_per_step": round(el_mb / a.steps * 1e3, 3)},
+                  "ms_per_step": round(el_m / a.steps * 1e3, 3), **b2b_m,
                   "hrw_gather": {"launches": mg_n, "avg_ms": round(mg_avg, 4),
                                  "host_write_GBps": round(out_bytes / (mg_avg / 1e3) / 1e9, 2) if mg_avg else None},
                   "locs_match_copy_path": m_ok,
@@ -1667,8 +1727,9 @@ def run_hrw(a, D, T, rank, world, res):
     copy_back = {"value": round(world * n * a.steps / elapsed, 1), "unit": "digests/s",
                  "ms_per_step": round(elapsed / a.steps * 1e3, 3), "host_enqueue_us": round(enqueue_us, 1),
                  "hrw_gather": {"launches": gn, "avg_ms": round(gms / max(gn, 1), 4)},
-                 "back_to_back": {"value": round(world * n * a.steps / el_b2b, 1),
-                                  "ms_per_step": round(el_b2b / a.steps * 1e3, 3), "locs_match_serial": b2b_ok},
+                 **({"back_to_back": {"value": round(world * n * a.steps / el_b2b, 1),
+                                      "ms_per_step": round(el_b2b / a.steps * 1e3, 3), "locs_match_serial": b2b_ok}}
+                    if a.full else {}),
                  "what": "locs and counts in HBM, the owner lists copied into pinned host memory on the same "
                          "stream behind the gather (hipMemcpyAsync D2H), one wait a step; back_to_back: step k+1 "
                          "enqueued on the other stream (its own outputs) before the host waits for step k"}
@@ -1676,6 +1737,7 @@ def run_hrw(a, D, T, rank, world, res):
     # written there by the gather when that is measured faster (and it works), else copied.
     use_mapped = "error" not in mapped and mapped["value"] >= copy_back["value"]
     main = mapped if use_mapped else copy_back
+    dump_outputs(a, rank, {"owner_lists": mapped_locs if use_mapped else want_locs})
     res.update({"metric": "hashring placement digests/s (C5)", "value": main["value"],
                 "unit": "digests/s", "steps": a.steps, "ms_per_step": main["ms_per_step"],
                 "higher_is_better": True, "scaling": "weak", "dtype": "u64+f64",
@@ -1688,7 +1750,8 @@ def run_hrw(a, D, T, rank, world, res):
                            "owner_index_bytes": isz},
                 "kernels": {"hrw_order": {"launches": hn, "avg_ms": round(hms / max(hn, 1), 3)},
                             "hrw_gather": main["hrw_gather"]},
-                "back_to_back": main["back_to_back"], "mapped_outputs": mapped, "copy_back": copy_back})
+                **({"back_to_back": main["back_to_back"]} if a.full else {}),
+                "mapped_outputs": mapped, "copy_back": copy_back})
     # Roofline of the per-digest kernel.  Device outputs: HBM-bound (32-B digest record in, R
     # owner indices + a count out).  Outputs in host memory: the gather's stores cross the
     # link, so the link's D2H rate bounds it.  The shard-table kernel's work is fixed (65,536
@@ -1768,6 +1831,72 @@ def hrw_sweep(D, dbuf, dig, n, steps):
     return out
 
 
+def files_other_paths(D, T, world, paths, lens, P, srcs, sums_f, dg_f):
+    """run_files' batch by the other routes: the same bytes from pinned host memory
+    (krk_metainfo_digest_host, staged and gathered) and from the files with the library's
+    default host offload (AUTO); every route's outputs against the timed pass's, and three
+    blobs against hashlib and the oracle."""
+    n, SRC, total = len(lens), len(srcs), int(sum(lens))
+    pins = []
+    for x in srcs:
+        pa = D.PinnedArray((x.size,), np.uint8)
+        pa.a[:] = x
+        pins.append(pa)
+    datas = [pins[i % SRC].a[:lens[i]] for i in range(n)]
+    D.metainfo_digest_host(datas, P)
+    # pinned blobs: the library's default gathers the wide windows from the caller's pages
+    # (one launch a window); KRK_HOST_GATHER=0's staging copy beside it (VERDICT r04 item 3)
+    pinned_paths = {}
+    for name, mode in (("staged", 0), ("gather", -1)):
+        D.set_host_gather(mode)
+        try:
+            T.barrier()
+            c0, t0 = cpu_seconds(), time.perf_counter()
+            sums_p, dg_p = D.metainfo_digest_host(datas, P)
+            cpu_p = cpu_seconds() - c0
+            T.barrier()
+            el_p = T.max_over_ranks(time.perf_counter() - t0)
+            st_p = D.windows_last_call()
+        finally:
+            D.set_host_gather(-1)
+        pinned_paths[name] = {"GBps": round(world * total / el_p / 1e9, 3),
+                              "host_cpu_s_per_GB": round(cpu_p / (total / 1e9), 4),
+                              "windows": st_p["windows"], "gather_windows": st_p["gather_windows"]}
+    D.set_sha_host_offload(-1)
+    try:
+        T.barrier()
+        t0 = time.perf_counter()
+        sums_a, dg_a = D.metainfo_digest_files(paths, lens, P)
+        T.barrier()
+        el_a = T.max_over_ranks(time.perf_counter() - t0)
+        st_a = D.windows_last_call()
+    finally:
+        D.set_sha_host_offload(0)
+    same = (np.array_equal(dg_f, dg_p) and np.array_equal(dg_f, dg_a) and
+            all(np.array_equal(x, y) and np.array_equal(x, z) for x, y, z in zip(sums_f, sums_p, sums_a)))
+    from oracle import oracle as O  # checker only
+    O.build()
+    import hashlib
+    L = np.asarray(lens)
+    ok = True
+    for i in sorted({int(L.argmin()), int(L.argmax()), n // 2}):
+        x = srcs[i % SRC][:lens[i]]
+        ok = ok and bytes(dg_f[i]) == hashlib.sha256(x.tobytes()).digest() and np.array_equal(
+            sums_f[i], O.calc_piece_sums(x, P)[1])
+    del pins, datas
+    return {"pinned_host_memory": {"value": round(world * total / el_p / 1e9, 3), "unit": "GB/s",
+                                   "roofline": link_roofline(D, world * total / el_p / 1e9, world=world),
+                                   "windows": st_p, "paths": pinned_paths,
+                                   "what": "the same blobs from pinned host memory (krk_metainfo_digest_host): "
+                                           "value = the library's default (wide windows gathered from the "
+                                           "caller's pages, gather.hip); paths.staged = KRK_HOST_GATHER=0 "
+                                           "(pinned -> pinned window copies, then the DMA)"},
+            "default_offload": {"value": round(world * total / el_a / 1e9, 3), "unit": "GB/s",
+                                "host_blobs": st_a["host_blobs"],
+                                "what": "krk_metainfo_digest_files with the library's default host offload (AUTO)"},
+            "outputs_equal_across_paths": bool(same), "oracle_sampled_match": bool(ok)}
+
+
 def run_files(a, D, T, rank, world, res):
     """The f3 file leg (krk_metainfo_digest_files): the C3 length law / 64 from
     files on the box's disk (page cache warm after the first pass).  value = blob bytes / time
@@ -1813,56 +1942,14 @@ def run_files(a, D, T, rank, world, res):
             crc_n, crc_ms = D.KernelTimer.stats("crc32_pieces")
         elapsed = T.timed_region(t1 - t0)
         value = world * total * a.steps / elapsed / 1e9
-        # the same bytes from pinned host memory, and the library's default (AUTO offload)
-        pins = []
-        for x in srcs:
-            pa = D.PinnedArray((x.size,), np.uint8)
-            pa.a[:] = x
-            pins.append(pa)
-        datas = [pins[i % SRC].a[:lens[i]] for i in range(n)]
-        D.metainfo_digest_host(datas, P)
-        # pinned blobs: the library's default gathers the wide windows from the caller's pages
-        # (one launch a window); KRK_HOST_GATHER=0's staging copy beside it
-        pinned_paths = {}
-        for name, mode in (("staged", 0), ("gather", -1)):
-            D.set_host_gather(mode)
-            try:
-                T.barrier()
-                c0, t0 = cpu_seconds(), time.perf_counter()
-                sums_p, dg_p = D.metainfo_digest_host(datas, P)
-                cpu_p = cpu_seconds() - c0
-                T.barrier()
-                el_p = T.max_over_ranks(time.perf_counter() - t0)
-                st_p = D.windows_last_call()
-            finally:
-                D.set_host_gather(-1)
-            pinned_paths[name] = {"GBps": round(world * total / el_p / 1e9, 3),
-                                  "host_cpu_s_per_GB": round(cpu_p / (total / 1e9), 4),
-                                  "windows": st_p["windows"], "gather_windows": st_p["gather_windows"]}
-        D.set_sha_host_offload(-1)
-        try:
-            T.barrier()
-            t0 = time.perf_counter()
-            sums_a, dg_a = D.metainfo_digest_files(paths, lens, P)
-            T.barrier()
-            el_a = T.max_over_ranks(time.perf_counter() - t0)
-            st_a = D.windows_last_call()
-        finally:
-            D.set_sha_host_offload(0)
-        same = (np.array_equal(dg_f, dg_p) and np.array_equal(dg_f, dg_a) and
-                all(np.array_equal(x, y) and np.array_equal(x, z) for x, y, z in zip(sums_f, sums_p, sums_a)))
-        from oracle import oracle as O  # checker only
-        O.build()
-        import hashlib
-        L = np.asarray(lens)
-        ok = True
-        for i in sorted({int(L.argmin()), int(L.argmax()), n // 2}):
-            x = srcs[i % SRC][:lens[i]]
-            ok = ok and bytes(dg_f[i]) == hashlib.sha256(x.tobytes()).digest() and np.array_equal(
-                sums_f[i], O.calc_piece_sums(x, P)[1])
-        del pins, datas
+        if a.dump_outputs:
+            dump_outputs(a, rank, {"piece_sums": np.concatenate([np.asarray(s, np.uint32) for s in sums_f]),
+                                   "digests": np.asarray(dg_f, np.uint8).reshape(n, 32)})
+        extras = files_other_paths(D, T, world, paths, lens, P, srcs, sums_f, dg_f) if a.full else {}
         cb = None
         if rank == 0 and not a.no_cpu_baseline:
+            from oracle import oracle as O  # the CPU baseline leg (test infrastructure)
+            O.build()
             # the reference's two reads of every file on the CPU budget: uploader.verify's
             # Digester over the upload file, then Generate's calcPieceSums over the cache file
             t_c, s_c, off_c, dg_c = O.baseline_files(paths, lens, P, node_cores(), passes=3)
@@ -1885,21 +1972,11 @@ def run_files(a, D, T, rank, world, res):
                 "config": {"workload": WORKLOADS[a.workload]["desc"], "blobs_per_gpu": n, "bytes_per_gpu": total,
                            "piece_length": P, "mode": "files -> pinned windows -> GPU (offload off)",
                            "parallelism": f"blob-sharded x{world}, no collective"},
-                "roofline": link_roofline(D, value, "files", n, world=world),
+                # the link's rate is timed by copies of its own (host_link_peak)
+                **({"roofline": link_roofline(D, value, "files", n, world=world)} if a.full else {}),
                 "windows": st, "kernels": {"sha256_multi": {"launches": sha_n, "avg_ms": round(sha_ms / max(sha_n, 1), 3)},
                                            "crc32_pieces": {"launches": crc_n, "avg_ms": round(crc_ms / max(crc_n, 1), 3)}},
-                "host_cpu_s_per_GB": round(c_f / a.steps / (total / 1e9), 4),
-                "pinned_host_memory": {"value": round(world * total / el_p / 1e9, 3), "unit": "GB/s",
-                                       "roofline": link_roofline(D, world * total / el_p / 1e9, world=world),
-                                       "windows": st_p, "paths": pinned_paths,
-                                       "what": "the same blobs from pinned host memory (krk_metainfo_digest_host): "
-                                               "value = the library's default (wide windows gathered from the "
-                                               "caller's pages, gather.hip); paths.staged = KRK_HOST_GATHER=0 "
-                                               "(pinned -> pinned window copies, then the DMA)"},
-                "default_offload": {"value": round(world * total / el_a / 1e9, 3), "unit": "GB/s",
-                                    "host_blobs": st_a["host_blobs"],
-                                    "what": "krk_metainfo_digest_files with the library's default host offload (AUTO)"},
-                "outputs_equal_across_paths": bool(same), "oracle_sampled_match": bool(ok)})
+                "host_cpu_s_per_GB": round(c_f / a.steps / (total / 1e9), 4), **extras})
     if cb:
         res["cpu_baseline"] = cb
 
@@ -1916,6 +1993,7 @@ sys.path.insert(0, ".")
 from kraken_amd import device as D
 from kraken_amd._capi import KRK_OFFLOAD_AUTO, KRK_PLACE_HOST, check, lib
 RUNS = int(sys.argv[1])
+FULL = len(sys.argv) < 3 or sys.argv[2] == "1"  # "0": the C1 time alone (a plain bench run)
 D.set_device(0)
 t = C.c_int(0)
 check(lib.krk_sha_host_offload(C.byref(t)))
@@ -1923,7 +2001,6 @@ assert t.value == KRK_OFFLOAD_AUTO, t.value
 L, P = 1 << 30, 4 << 20
 arena = D.BlobArena([L], P, blob_ids=[7])
 out = D.BatchOutputs(arena)
-host = arena.buf.to_host(np.uint8, L)
 res = {"blob_bytes": L, "piece_length": P, "runs": RUNS}
 
 def best(f, k=RUNS):
@@ -1931,6 +2008,16 @@ def best(f, k=RUNS):
     for _ in range(k):
         t0 = time.perf_counter(); f(); ts.append(time.perf_counter() - t0)
     return min(ts)
+
+def c1():  # C1 through the device-resident drop-in, defaults
+    D.metainfo_digest(arena, out)
+    D.synchronize()
+if not FULL:
+    res["c1_metainfo_digest_dev_s"] = best(c1)
+    res["c1_GBps"] = L / res["c1_metainfo_digest_dev_s"] / 1e9
+    print(json.dumps(res))
+    sys.exit(0)
+host = arena.buf.to_host(np.uint8, L)
 # one host thread, the same bytes: SHA-NI (krk_host_sha256) and PCLMUL (krk_host_crc32_update)
 o32 = (C.c_uint8 * 32)()
 res["host_sha_1thread_s"] = best(lambda: lib.krk_host_sha256(host.ctypes.data, L, o32))
@@ -1940,9 +2027,6 @@ c = C.c_uint32()
 res["host_crc_1thread_s"] = best(lambda: lib.krk_host_crc32_update(0, host.ctypes.data, L, C.byref(c)))
 assert c.value == zlib.crc32(host)
 
-def c1():  # C1 through the device-resident drop-in, defaults
-    D.metainfo_digest(arena, out)
-    D.synchronize()
 res["c1_metainfo_digest_dev_s"] = best(c1)
 dg = out.digests.to_host(np.uint8, 32)
 sums = out.sums.to_host(np.uint32, arena.total_pieces)
@@ -1980,10 +2064,12 @@ print(json.dumps(res))
 """
 
 
-def run_defaults_probe(runs=3):
-    """DEFAULTS_PROBE in a fresh child process with every KRK_ variable removed."""
+def run_defaults_probe(runs=3, full=True):
+    """DEFAULTS_PROBE in a fresh child process with every KRK_ variable removed; full=False
+    times C1 alone (no host-thread times, no piece stream, no output checks)."""
     env = {k: v for k, v in os.environ.items() if not k.startswith("KRK_")}
-    r = subprocess.run([sys.executable, "-c", DEFAULTS_PROBE, str(runs)], capture_output=True, text=True, cwd=ROOT,
+    r = subprocess.run([sys.executable, "-c", DEFAULTS_PROBE, str(runs), str(int(full))], capture_output=True,
+                       text=True, cwd=ROOT,
                        env=env, timeout=600)
     if r.returncode != 0:
         raise RuntimeError("defaults probe failed: " + r.stdout[-2000:] + r.stderr[-3000:])
@@ -1996,7 +2082,7 @@ def run_defaults(a, D, T, rank, world, res):
     one host thread of the reference's own placement on the same bytes.  value = C1 GB/s
     with the defaults; the line carries the VERDICT r03 item 1 criteria as measured booleans
     (C1 within 1.2x of one SHA-NI thread, the stream at least one PCLMUL thread)."""
-    p = run_defaults_probe(runs=max(1, a.steps))
+    p = run_defaults_probe(runs=max(1, a.steps), full=a.full)
     el = T.timed_region(p["c1_metainfo_digest_dev_s"])
     res.update({"metric": "defaults: C1 NewMetaInfo+digest GB/s (library defaults, fresh process)",
                 "value": round(world * p["blob_bytes"] / el / 1e9, 3), "unit": "GB/s", "steps": a.steps,
@@ -2005,8 +2091,9 @@ def run_defaults(a, D, T, rank, world, res):
                 "config": {"workload": WORKLOADS[a.workload]["desc"], "blob_bytes": p["blob_bytes"],
                            "piece_length": p["piece_length"], "knobs": "none (KRK_ environment removed)"},
                 "defaults": {k: (round(v, 4) if isinstance(v, float) else v) for k, v in p.items()},
-                "criteria": {"c1_within_1.2x_one_sha_thread": p["c1_ratio_to_host_sha"] <= 1.2,
-                             "stream_at_least_one_crc_thread": p["stream_GBps"] >= p["host_crc_1thread_GBps"]}})
+                **({"criteria": {"c1_within_1.2x_one_sha_thread": p["c1_ratio_to_host_sha"] <= 1.2,
+                                 "stream_at_least_one_crc_thread": p["stream_GBps"] >= p["host_crc_1thread_GBps"]}}
+                   if a.full else {})})
 
 
 def drop_cache(paths):
@@ -2387,6 +2474,12 @@ def main():
     ap.add_argument("--steps", type=int, default=None, help="timed steps (default 3; C5: 50)")
     ap.add_argument("--warmup", type=int, default=None, help="untimed steps (default 1; C5: 5)")
     ap.add_argument("--workload", default="c2", choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also every other leg of the workload (CPU baseline, host-offload, "
+                         "end-to-end and back-to-back legs, sweeps, the live SHA issue ceiling, checks against the "
+                         "oracle), each under its own --no-* switch; a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to its caller as DIR/<name>.npy (float32/float64)")
     ap.add_argument("--blobs", type=int, default=0, help="override the blob (or digest) count")
     ap.add_argument("--nodes", type=int, default=16, help="C5: origins in the ring")
     ap.add_argument("--window-gib", type=int, default=48, help="C3: device window size")
@@ -2437,6 +2530,13 @@ def main():
         a.steps = WORKLOADS[a.workload].get("steps", 3)
     if a.warmup is None:
         a.warmup = WORKLOADS[a.workload].get("warmup", 1)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if a.dump_outputs and WORKLOADS[a.workload]["kind"] in ("engine", "defaults"):
+        ap.error(f"--dump-outputs: the {a.workload} workload's outputs stay in its child processes")
+    if not a.full:  # a plain run: set up, warm up, time the steps, print the line
+        a.no_cpu_baseline = a.no_e2e = a.no_offload = a.no_sweep = a.no_ceiling = True
+        a.cold_gib = 0.0
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(a.gpus, sys.argv[1:], rehearse=a.rehearse))

@@ -108,7 +108,7 @@ def test_launcher_env_budget_and_baseline_cores(tmp_path, monkeypatch):
     # a torch.distributed.run-shaped environment: OMP_NUM_THREADS=1 a rank
     monkeypatch.setenv("OMP_NUM_THREADS", "1")
     monkeypatch.delenv("KRK_HOST_CPUS", raising=False)
-    args = [ROOT, str(tmp_path), "--gpus", str(world), "--rehearse", "--workload", "small", "--blobs", str(node),
+    args = [ROOT, str(tmp_path), "--full", "--gpus", str(world), "--rehearse", "--workload", "small", "--blobs", str(node),
             "--steps", "1", "--warmup", "0", "--cpu-seconds", "0.2", "--no-e2e", "--no-ceiling"]
     assert bench.spawn_ranks(world, args, devices=1, rehearse=True, script=str(script)) == 0
     want = max(1, node // world)

@@ -14,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_json_line_contract(gpu):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "small", "--steps", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--workload", "small", "--steps", "2",
                         "--warmup", "1", "--cpu-seconds", "1", "--e2e-mb", "4"],
                        capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -36,6 +36,42 @@ def test_bench_json_line_contract(gpu):
     assert cb["outputs_match_gpu"] is True
 
 
+def test_plain_run_times_the_steps_only_and_dumps_outputs(gpu, orc, tmp_path):
+    """Without --full the line carries the headline of the timed steps and none of the other
+    legs; --dump-outputs writes the last step's piece sums (float64) and digests (float32),
+    here checked against hashlib and the oracle over the same synthetic blobs."""
+    import hashlib
+
+    import numpy as np
+
+    O = orc
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "small",
+                        "--blobs", "5", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / "out")],
+                       capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert d["unit"] == "GB/s" and d["higher_is_better"] is True and d["dtype"] == "u8"
+    want = d["config"]["bytes_per_gpu"] / (d["ms_per_step"] / 1e3) / 1e9
+    # both figures are rounded to three decimals: half a unit of the last place of `value`,
+    # plus that of ms_per_step (relative 0.0005 / ms_per_step) carried through the division
+    tol = 0.5e-3 + want * 0.5e-3 / d["ms_per_step"] + 1e-9
+    assert abs(d["value"] - want) <= tol, (d["value"], want, tol)
+    assert d["kernels"]["sha256_multi"]["launches"] >= 2 and d["kernels"]["crc32_pieces"]["launches"] >= 2
+    for k in ("cpu_baseline", "end_to_end", "host_offload"):
+        assert k not in d, k
+    assert "issue_bound" not in d["roofline"] or "ceiling_per_stream_MBps" not in d["roofline"]["issue_bound"]
+    dg = np.load(tmp_path / "out" / "digests.npy")
+    sums = np.load(tmp_path / "out" / "piece_sums.npy")
+    assert dg.dtype == np.float32 and dg.shape == (5, 32) and sums.dtype == np.float64 and sums.shape == (5 * 4,)
+    for i in range(5):
+        data = O.synth(i, 16 << 20)
+        assert bytes(dg[i].astype(np.uint8)) == hashlib.sha256(data.tobytes()).digest(), i
+        assert np.array_equal(sums[4 * i:4 * i + 4], np.asarray(O.calc_piece_sums(data, 4 << 20)[1], np.float64)), i
+
+
 def test_bench_gpus_2_spawns_two_ranks(gpu):
     """`bench.py --gpus 2` with no launcher spawns two rank processes (here sharing the
     one GPU: --rehearse) and reports the whole job: n_gpus == 2 and value == both
@@ -45,8 +81,8 @@ def test_bench_gpus_2_spawns_two_ranks(gpu):
     one GPU, which only a rehearsal may."""
     env = dict(os.environ, OMP_NUM_THREADS="1")  # what torch.distributed.run gives each rank of a node
     env.pop("KRK_HOST_CPUS", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rehearse", "--blobs", "20",
-                        "--steps", "1", "--warmup", "1", "--cpu-seconds", "1", "--no-e2e", "--no-ceiling"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--rehearse",
+                        "--blobs", "20", "--steps", "1", "--warmup", "1", "--cpu-seconds", "1", "--no-e2e", "--no-ceiling"],
                        capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -23,19 +23,19 @@ for step in "$@"; do
     all) run pytest_all 900 $PYT tests -m gpu ;;
     crossover) run crc_crossover 300 tests/native/crc_crossover ;;
     defaults) run pytest_defaults 300 $PYT tests/test_gpu_defaults.py tests/test_gpu_bindings.py ;;
-    bench) run bench_c2 300 python bench.py ;;
-    bench_c1) run bench_c1 300 python bench.py --workload c1 --steps 2 --warmup 1 ;;
-    bench_files) run bench_files 600 python bench.py --workload files --steps 2 --warmup 1 ;;
-    bench_engine) run bench_engine 300 python bench.py --workload engine ;;
-    bench_c4) run bench_c4 600 python bench.py --workload c4 ;;
-    bench_c5regen) run bench_c5regen 600 python bench.py --workload c5regen ;;
-    bench_f1) run bench_f1verify 600 python bench.py --workload f1verify ;;
+    bench) run bench_c2 300 python bench.py --full ;;
+    bench_c1) run bench_c1 300 python bench.py --full --workload c1 --steps 2 --warmup 1 ;;
+    bench_files) run bench_files 600 python bench.py --full --workload files --steps 2 --warmup 1 ;;
+    bench_engine) run bench_engine 300 python bench.py --full --workload engine ;;
+    bench_c4) run bench_c4 600 python bench.py --full --workload c4 ;;
+    bench_c5regen) run bench_c5regen 600 python bench.py --full --workload c5regen ;;
+    bench_f1) run bench_f1verify 600 python bench.py --full --workload f1verify ;;
     verify_tests) run pytest_verify 400 $PYT tests/test_gpu_agent_verify.py tests/test_gpu_files.py -k "split or placements or verify" ;;
-    bench_c3) run bench_c3 900 python bench.py --workload c3 ;;
-    bench_c5) run bench_c5 300 python bench.py --workload c5 ;;
-    bench_c5regen_digest) run bench_c5regen_digest 400 python bench.py --workload c5regen_digest ;;
+    bench_c3) run bench_c3 900 python bench.py --full --workload c3 ;;
+    bench_c5) run bench_c5 300 python bench.py --full --workload c5 ;;
+    bench_c5regen_digest) run bench_c5regen_digest 400 python bench.py --full --workload c5regen_digest ;;
     pinned_ab) run pinned_ab 400 python tools/pinned_ab.py 48 192 ;;
-    e2e_w2 | e2e_w3 | e2e_w4) run $step 300 env KRK_STAGING_WINDOWS=${step#e2e_w} python bench.py --e2e-only --no-cpu-baseline ;;
+    e2e_w2 | e2e_w3 | e2e_w4) run $step 300 env KRK_STAGING_WINDOWS=${step#e2e_w} python bench.py --full --e2e-only --no-cpu-baseline ;;
     # rocprofv3 on the end-to-end legs (kernel trace + copy trace; PMC passes on their own runs)
     prof_e2e) run prof_e2e 400 rocprofv3 --kernel-trace --memory-copy-trace --stats --output-format csv \
                   -d gpurun_out/prof_e2e -- python3 bench.py --e2e-only --no-cpu-baseline ;;

@@ -23,30 +23,30 @@ for step in "$@"; do
     gather) run gather_probe 240 tools/micro/gather_probe 8 16 ;;
     disk) run disk_info 60 bash -c 'df -h . /tmp /dev/shm; lsblk -o NAME,SIZE,ROTA,TYPE,MOUNTPOINT 2>/dev/null | head -30; free -g; nproc; cat /sys/fs/cgroup/cpu.max; cat /sys/fs/cgroup/memory.max; mount | grep -E " / | /tmp " ; echo; ls -la /mnt /scratch /local 2>/dev/null | head' ;;
     ddtest) run dd_test 300 bash -c 'd=$(mktemp -d -p .); dd if=/dev/zero of=$d/f bs=64M count=96 oflag=direct conv=fsync 2>&1 | tail -1; sync; dd if=$d/f of=/dev/null bs=64M iflag=direct 2>&1 | tail -1; rm -rf $d' ;;
-    bench) run bench_c2 300 python bench.py ;;
-    bench_engine) run bench_engine 900 python bench.py --workload engine ;;
-    bench_engine_zc) run bench_engine_zc 900 env KRK_ENGINE_SLOT_SRC=zerocopy python bench.py --workload engine ;;
-    bench_engine_gather) run bench_engine_gather 900 env KRK_ENGINE_SLOT_SRC=gather python bench.py --workload engine ;;
+    bench) run bench_c2 300 python bench.py --full ;;
+    bench_engine) run bench_engine 900 python bench.py --full --workload engine ;;
+    bench_engine_zc) run bench_engine_zc 900 env KRK_ENGINE_SLOT_SRC=zerocopy python bench.py --full --workload engine ;;
+    bench_engine_gather) run bench_engine_gather 900 env KRK_ENGINE_SLOT_SRC=gather python bench.py --full --workload engine ;;
     diskprobe) run disk_probe 400 bash -c 'd=$(mktemp -d -p .); tools/micro/disk_probe $d 32; rc=$?; rm -rf $d; exit $rc' ;;
     hostmem) run host_mem_probe 400 tools/micro/host_mem_probe 8 16 ;;
     regprobe) run reg_probe 300 tools/micro/reg_probe 8 ;;
     gather_tests) run pytest_gather 600 $PYT tests/test_gpu_gather.py tests/test_gpu_files.py tests/test_gpu_agent_verify.py tests/test_gpu_bindings.py tests/test_gpu_bench_contract.py ;;
     engine_tests) run pytest_engine 600 $PYT tests/test_gpu_engine.py tests/test_gpu_concurrency.py tests/test_gpu_bindings.py tests/test_gpu_digest_metainfo.py ;;
-    tail_trace) run tail_trace 400 env KRK_TRACE=1 python bench.py --no-e2e --no-cpu-baseline ;;
-    hyb_sweep) run hyb_sweep 600 env KRK_BENCH_HYBRID=-1,6,8,10,12 python bench.py --e2e-only --no-cpu-baseline ;;
-    bench_defaults) run bench_defaults 300 python bench.py --workload defaults ;;
-    bench_files) run bench_files 900 python bench.py --workload files --steps 2 --warmup 1 ;;
-    bench_c4) run bench_c4 600 python bench.py --workload c4 ;;
-    bench_c3) run bench_c3 900 python bench.py --workload c3 ;;
-    bench_c5) run bench_c5 300 python bench.py --workload c5 ;;
-    bench_c5regen) run bench_c5regen 600 python bench.py --workload c5regen ;;
-    bench_c5regen_digest) run bench_c5regen_digest 400 python bench.py --workload c5regen_digest ;;
-    bench_f1) run bench_f1verify 600 python bench.py --workload f1verify ;;
-    bench_c1) run bench_c1 300 python bench.py --workload c1 --steps 2 --warmup 1 ;;
+    tail_trace) run tail_trace 400 env KRK_TRACE=1 python bench.py --full --no-e2e --no-cpu-baseline ;;
+    hyb_sweep) run hyb_sweep 600 env KRK_BENCH_HYBRID=-1,6,8,10,12 python bench.py --full --e2e-only --no-cpu-baseline ;;
+    bench_defaults) run bench_defaults 300 python bench.py --full --workload defaults ;;
+    bench_files) run bench_files 900 python bench.py --full --workload files --steps 2 --warmup 1 ;;
+    bench_c4) run bench_c4 600 python bench.py --full --workload c4 ;;
+    bench_c3) run bench_c3 900 python bench.py --full --workload c3 ;;
+    bench_c5) run bench_c5 300 python bench.py --full --workload c5 ;;
+    bench_c5regen) run bench_c5regen 600 python bench.py --full --workload c5regen ;;
+    bench_c5regen_digest) run bench_c5regen_digest 400 python bench.py --full --workload c5regen_digest ;;
+    bench_f1) run bench_f1verify 600 python bench.py --full --workload f1verify ;;
+    bench_c1) run bench_c1 300 python bench.py --full --workload c1 --steps 2 --warmup 1 ;;
     # the LDS-DMA CRC variants live in the diagnostic build (make -C kraken_amd/csrc diag)
     crc_parity) run crc_parity 600 env KRK_CRC_VARIANT=20 KRK_LIB_PATH=kraken_amd/lib/diag/libkraken_hip.so $PYT tests/test_gpu_pieces.py tests/test_gpu_full_size.py tests/test_gpu_digest_metainfo.py ;;
-    crc_ab) for v in 16 20 21 16 20 21; do run crc_c4_v$v.$RANDOM 300 env KRK_CRC_VARIANT=$v KRK_LIB_PATH=kraken_amd/lib/diag/libkraken_hip.so python bench.py --workload c4 --no-cpu-baseline --no-e2e; done ;;
-    crc_ab2) for v in 16 22 23 16 22 23; do run crc_c4_v$v.$RANDOM 300 env KRK_CRC_VARIANT=$v KRK_LIB_PATH=kraken_amd/lib/diag/libkraken_hip.so python bench.py --workload c4 --no-cpu-baseline --no-e2e; done ;;
+    crc_ab) for v in 16 20 21 16 20 21; do run crc_c4_v$v.$RANDOM 300 env KRK_CRC_VARIANT=$v KRK_LIB_PATH=kraken_amd/lib/diag/libkraken_hip.so python bench.py --full --workload c4 --no-cpu-baseline --no-e2e; done ;;
+    crc_ab2) for v in 16 22 23 16 22 23; do run crc_c4_v$v.$RANDOM 300 env KRK_CRC_VARIANT=$v KRK_LIB_PATH=kraken_amd/lib/diag/libkraken_hip.so python bench.py --full --workload c4 --no-cpu-baseline --no-e2e; done ;;
     crc_parity22 | crc_parity23) v=${step#crc_parity}
         run crc_parity$v 600 env KRK_CRC_VARIANT=$v KRK_LIB_PATH=kraken_amd/lib/diag/libkraken_hip.so $PYT tests/test_gpu_pieces.py tests/test_gpu_full_size.py ;;
     # rocprofv3 summaries (kernel trace + copy trace; PMC passes on their own runs)

@@ -14,7 +14,7 @@ done
 for nw in 3 4; do
   for mb in 512 1024; do
     out=gpurun_out/ring_sweep/files_w${nw}_mb${mb}.log
-    KRK_STAGING_WINDOWS=$nw KRK_WINDOW_MB=$mb timeout -k 10 300 python bench.py --workload files --steps 2 --warmup 1 --no-cpu-baseline > $out 2>&1 || { echo "failed $out"; exit 1; }
+    KRK_STAGING_WINDOWS=$nw KRK_WINDOW_MB=$mb timeout -k 10 300 python bench.py --full --workload files --steps 2 --warmup 1 --no-cpu-baseline > $out 2>&1 || { echo "failed $out"; exit 1; }
     echo "files w=$nw mb=$mb $(grep -o '"value": [0-9.]*' $out | head -1)"
   done
 done
