@@ -1,6 +1,7 @@
 // runtime.hpp -- internal to libkraken_hip: device contexts, the stream-ordered
 // scratch cache, the CRC work builder and the SHA job runner shared by the C ABI
-// (runtime.cpp) and the submission engine (engine.cpp).  Not part of the ABI.
+// (runtime.cpp, batch_dev.cpp, crc_host.cpp, placement.cpp, windows.cpp) and the
+// submission engine (engine.cpp).  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <sched.h>
@@ -47,6 +48,28 @@ void set_error(int code, const char* fmt, ...);
             return code;                  \
         }                                 \
     } while (0)
+
+// A HIP event owned by one call: destroyed on every return path.
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(Event&& o) noexcept : e(o.e) { o.e = nullptr; }
+    Event& operator=(Event&& o) noexcept {
+        std::swap(e, o.e);
+        return *this;
+    }
+    Event(const Event&) = delete;
+    Event& operator=(const Event&) = delete;
+    ~Event() {
+        if (e) hipEventDestroy(e);
+    }
+    hipError_t create(unsigned flags = hipEventDisableTiming) {
+        const hipError_t r = hipEventCreateWithFlags(&e, flags);
+        if (r != hipSuccess) e = nullptr;
+        return r;
+    }
+    operator hipEvent_t() const { return e; }
+};
 
 // ------------------------------------------------------------------ timing
 enum Kern { K_CRC, K_SHA, K_HRW, K_FILTER, K_GATHER, K_SYNTH, K_HOSTG, K_N };
@@ -266,7 +289,7 @@ struct Pipeline;
 struct Engine;
 struct OffloadPool;
 
-struct OwnerTables;  // runtime.cpp
+struct OwnerTables;  // placement.cpp
 struct Device {
     // Submission engine (engine.cpp): the batching queues of the streaming
     // Digester / piece-stream / crc32.Update calls, created on first use.
@@ -289,7 +312,7 @@ struct Device {
     uint8_t* shard_bad = nullptr;
     std::once_flag shard_once;
     int shard_rc = 0;
-    // ring.Locations owner tables by membership (runtime.cpp OwnerTables): the reference's
+    // ring.Locations owner tables by membership (placement.cpp OwnerTables): the reference's
     // Ring rebuilds its hrw only on Refresh (lib/hashring/ring.go:141-165).
     OwnerTables* owners = nullptr;
     std::mutex owners_mu;
@@ -583,21 +606,30 @@ struct ItemBuilder {
     }
 };
 
+// A blob's piece length and sums indices (krk_blob and krk_file_blob alike).
+template <class Blob>
+inline int validate_pieces(const Blob& b) {
+    KRK_CHECK(b.piece_length > 0, KRK_EINVAL, "piece length must be positive");
+    KRK_CHECK(b.sums_offset + krk_num_pieces(b.length, b.piece_length) <= 0xFFFFFFFFull, KRK_EINVAL,
+              "sums index exceeds 2^32 in one call");
+    return KRK_OK;
+}
+
 inline int validate_blobs(const krk_blob* blobs, uint64_t n) {
     KRK_CHECK(n == 0 || blobs, KRK_EINVAL, "blobs is NULL");
     for (uint64_t i = 0; i < n; ++i) {
         KRK_CHECK(blobs[i].piece_length > 0, KRK_EINVAL, "piece length must be positive");
         KRK_CHECK(blobs[i].length == 0 || blobs[i].data, KRK_EINVAL, "blob %llu: data is NULL",
                   (unsigned long long)i);
-        const uint64_t np = krk_num_pieces(blobs[i].length, blobs[i].piece_length);
-        KRK_CHECK(blobs[i].sums_offset + np <= 0xFFFFFFFFull, KRK_EINVAL,
-                  "sums index exceeds 2^32 in one call");
+        int r = validate_pieces(blobs[i]);
+        if (r) return r;
     }
     return KRK_OK;
 }
 
 // Zero the sums span [lo, hi) that the blobs cover.
-inline void sums_span(const krk_blob* blobs, uint64_t n, uint64_t* lo, uint64_t* hi) {
+template <class Blob>
+inline void sums_span(const Blob* blobs, uint64_t n, uint64_t* lo, uint64_t* hi) {
     *lo = UINT64_MAX;
     *hi = 0;
     for (uint64_t i = 0; i < n; ++i) {
@@ -826,6 +858,7 @@ struct TailSrc {
     const uint64_t* start;
     hipEvent_t gpu_done;
 };
+void owner_tables_teardown(Device& D);  // krk_shutdown: the cached owner tables (placement.cpp)
 void offload_teardown(Device& D);  // krk_shutdown: the offload threads' streams and pinned buffers
 void offload_hash_host(const std::vector<const uint8_t*>& ptrs, const std::vector<uint64_t>& lens, int threads,
                        uint8_t* out);

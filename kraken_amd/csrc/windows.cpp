@@ -608,18 +608,122 @@ uint64_t direct_live_cap(Device* D) {
 
 using namespace krk;
 
-// The device results, the host offload's results and the caller's arrays of one call.
+// What krk_metainfo_digest_host, krk_sha256_host and krk_metainfo_digest_files share: the
+// device results, the host offload's share with its thread and results, the caller's arrays.
+// An entry point checks its arguments, then plan(), start(), its filler, run().
 namespace {
-struct Outputs {
-    uint8_t* d_dig = nullptr;
+struct WindowCall {
+    const char* name;  // the entry point, in its error texts
+    uint64_t n;
+    uint32_t* sums_host;
+    uint8_t* digests_host;
+    bool crc;  // piece sums too (false: digests only, no sums buffer)
+    std::vector<uint64_t> lens, soff;
+    std::vector<int64_t> plens;
+    uint64_t lo = 0, hi = 0;  // the sums span
+    double resident = -1;       // file batches: CallStats' resident and direct_reads
+    bool direct_reads = false;
+    uint8_t* d_dig = nullptr;  // the device's results
     uint32_t *d_state = nullptr, *d_sums = nullptr;
     DevMem mem;
-    int alloc(uint64_t n, uint64_t hi) {
+    int off_t = 0;  // the host share's threads, blobs, results, thread and failure
+    std::vector<char> on_host;
+    std::vector<uint32_t> host, host_sums;
+    std::vector<uint8_t> host_dig;
+    std::vector<uint64_t> host_sums_off;
+    std::thread host_th;
+    int host_rc = KRK_OK;
+    std::string host_err;
+    const int saved_share = t_host_share;
+
+    template <class Blob>
+    WindowCall(const char* name_, const Blob* blobs, uint64_t n_, uint32_t* sums, uint8_t* digests, bool crc_ = true)
+        : name(name_), n(n_), sums_host(sums), digests_host(digests), crc(crc_), lens(n_), soff(n_), plens(n_),
+          on_host(n_, 0) {
+        for (uint64_t i = 0; i < n; ++i) {
+            lens[i] = blobs[i].length;
+            plens[i] = blobs[i].piece_length;
+            soff[i] = blobs[i].sums_offset;
+        }
+        if (crc) sums_span(blobs, n, &lo, &hi);
+    }
+    // the host thread writes this call's scratch: joined on every path before that goes
+    ~WindowCall() {
+        if (host_th.joinable()) host_th.join();
+        t_host_share = saved_share;
+    }
+
+    // The blobs that `threads` host threads take under `mode`, their scratch, the device outputs.
+    int plan(Device* D, int mode, int threads) {
+        KRK_CHECK(hi == lo || sums_host, KRK_EINVAL, "sums_host is NULL");
+        off_t = threads;
+        if (off_t > 0) host = offload_plan(lens.data(), n, off_t, planner_rates(D), nullptr, nullptr, mode);
+        for (uint32_t i : host) on_host[i] = 1;
         KRK_HIP(mem.alloc(&d_dig, n * 32));
         KRK_HIP(mem.alloc(&d_state, n * 32));
-        KRK_HIP(mem.alloc(&d_sums, std::max<uint64_t>(hi, 1) * 4));
-        KRK_HIP(hipMemset(d_sums, 0, std::max<uint64_t>(hi, 1) * 4));
+        if (crc) {
+            KRK_HIP(mem.alloc(&d_sums, std::max<uint64_t>(hi, 1) * 4));
+            KRK_HIP(hipMemset(d_sums, 0, std::max<uint64_t>(hi, 1) * 4));
+        }
+        host_dig.resize(32 * host.size());
+        host_sums_off.assign(host.size() + 1, 0);
+        for (size_t j = 0; crc && j < host.size(); ++j)
+            host_sums_off[j + 1] = host_sums_off[j] + krk_num_pieces(lens[host[j]], plens[host[j]]);
+        host_sums.resize(host_sums_off.back());
         return KRK_OK;
+    }
+    // work(lengths, piece lengths, sums destinations of the host blobs) -> int on the host
+    // thread, started before the windows; its failure is kept for run().
+    template <class F>
+    void start(F work) {
+        if (host.empty()) return;
+        host_th = std::thread([this, work] {
+            std::vector<uint64_t> l(host.size()), pl(host.size());
+            std::vector<uint32_t*> so(host.size());
+            for (size_t j = 0; j < host.size(); ++j) {
+                l[j] = lens[host[j]];
+                pl[j] = (uint64_t)plens[host[j]];
+                so[j] = host_sums.data() + host_sums_off[j];
+            }
+            host_rc = work(l, pl, so);
+            if (host_rc) host_err = t_err;
+        });
+        // The copy threads and the offload's threads share the process's CPU budget: above it
+        // a CPU quota throttles the whole process.
+        t_host_share = std::max(4, host_threads_for_call() - off_t);
+    }
+    // The windows, then both sides' results into the caller's arrays.  mem_filler: the filler
+    // when it reads caller memory (its registrations are released before any copy-out).
+    int run(Device* D, Filler& filler, MemFiller* mem_filler, uint64_t align, uint64_t cap) {
+        CallStats st;
+        int r = windows_pass(D, n, lens.data(), plens.data(), soff.data(), on_host, filler, align, cap, d_sums, d_dig,
+                             d_state, &st, crc);
+        st.resident = resident;
+        st.direct_reads = direct_reads;
+        // drain what was queued even after a read error (the windows' kernels read the buffers)
+        const bool synced = hipStreamSynchronize(D->s_a) == hipSuccess &&
+                            (!crc || hipStreamSynchronize(D->s_b) == hipSuccess) &&
+                            hipStreamSynchronize(D->s_main) == hipSuccess;
+        if (!r && !synced) {
+            set_error(KRK_EHIP, "%s: sync failed", name);
+            r = KRK_EHIP;
+        }
+        if (mem_filler) release_caller_pages(*mem_filler, &st);
+        if (!r) r = copy_out(digests_host, d_dig, n * 32, filler.registry(), "digest");
+        if (!r && hi > lo) r = copy_out(sums_host + lo, d_sums + lo, (hi - lo) * 4, filler.registry(), "sums");
+        if (host_th.joinable()) host_th.join();
+        if (!r && host_rc) {
+            t_err = host_err;
+            r = host_rc;
+        }
+        for (size_t q = 0; !r && q < host.size(); ++q) {
+            memcpy(digests_host + 32 * (size_t)host[q], &host_dig[32 * q], 32);
+            if (const uint64_t np = host_sums_off[q + 1] - host_sums_off[q])
+                memcpy(sums_host + soff[host[q]], &host_sums[host_sums_off[q]], np * 4);
+        }
+        st.host_blobs = host.size();
+        t_last_call = st;
+        return r;
     }
 };
 }  // namespace
@@ -691,82 +795,20 @@ int krk_metainfo_digest_host(const krk_blob* blobs, uint64_t n, uint32_t* sums_h
     if (r) return r;
     if (!n) return KRK_OK;
     KRK_CHECK(digests_host, KRK_EINVAL, "digests_host is NULL");
-    uint64_t lo, hi;
-    sums_span(blobs, n, &lo, &hi);
-    KRK_CHECK(hi == lo || sums_host, KRK_EINVAL, "sums_host is NULL");
-    std::vector<uint64_t> lens(n), soff(n);
-    std::vector<int64_t> plens(n);
-    for (uint64_t i = 0; i < n; ++i) {
-        lens[i] = blobs[i].length;
-        plens[i] = blobs[i].piece_length;
-        soff[i] = blobs[i].sums_offset;
-    }
+    WindowCall c("metainfo_digest_host", blobs, n, sums_host, digests_host);
     // SHA-256 host offload (KRK_OFFLOAD_AUTO by default): the planner's blobs are hashed and
     // piece-summed in place on host threads and never cross the host link.
-    std::vector<char> on_host(n, 0);
-    std::vector<uint32_t> host;
-    const int off_t = offload_threads(kOffHostWhole);
-    if (off_t > 0) {
-        host = offload_plan(lens.data(), n, off_t, planner_rates(D), nullptr, nullptr, kOffHostWhole);
-        for (uint32_t i : host) on_host[i] = 1;
-    }
-    Outputs o;
-    r = o.alloc(n, hi);
+    r = c.plan(D, kOffHostWhole, offload_threads(kOffHostWhole));
     if (r) return r;
-    std::vector<uint8_t> host_dig(32 * host.size());
-    std::vector<uint64_t> host_sums_off(host.size() + 1, 0);
-    for (size_t j = 0; j < host.size(); ++j)
-        host_sums_off[j + 1] = host_sums_off[j] + krk_num_pieces(lens[host[j]], plens[host[j]]);
-    std::vector<uint32_t> host_sums(host_sums_off.back());
-    std::thread host_th;
-    if (!host.empty())
-        host_th = std::thread([&] {
-            std::vector<const uint8_t*> p(host.size());
-            std::vector<uint64_t> l(host.size()), pl(host.size());
-            std::vector<uint32_t*> so(host.size());
-            for (size_t j = 0; j < host.size(); ++j) {
-                p[j] = blobs[host[j]].data;
-                l[j] = lens[host[j]];
-                pl[j] = (uint64_t)plens[host[j]];
-                so[j] = host_sums.data() + host_sums_off[j];
-            }
-            offload_whole_host(p, l, pl, so, off_t, host_dig.data());
-        });
-    struct Joiner {
-        std::thread& t;
-        ~Joiner() {
-            if (t.joinable()) t.join();
-        }
-    } joiner{host_th};
-    // The copy threads and the offload's threads share the process's CPU budget: above it
-    // a CPU quota throttles the whole process.
-    struct ShareGuard {
-        int saved;
-        ~ShareGuard() { t_host_share = saved; }
-    } share_guard{t_host_share};
-    if (!host.empty()) t_host_share = std::max(4, host_threads_for_call() - off_t);
+    c.start([&](auto& l, auto& pl, auto& so) {
+        std::vector<const uint8_t*> p;
+        for (uint32_t i : c.host) p.push_back(blobs[i].data);
+        offload_whole_host(p, l, pl, so, c.off_t, c.host_dig.data());
+        return KRK_OK;
+    });
     MemFiller filler(blobs);
-    setup_mem_filler(filler, blobs, n, on_host, D);
-    CallStats st;
-    r = windows_pass(D, n, lens.data(), plens.data(), soff.data(), on_host, filler, 64, live_cap_for(D), o.d_sums,
-                     o.d_dig, o.d_state, &st);
-    if (!r && (hipStreamSynchronize(D->s_a) != hipSuccess || hipStreamSynchronize(D->s_b) != hipSuccess ||
-               hipStreamSynchronize(D->s_main) != hipSuccess)) {
-        set_error(KRK_EHIP, "metainfo_digest_host: sync failed");
-        r = KRK_EHIP;
-    }
-    release_caller_pages(filler, &st);
-    if (!r) r = copy_out(digests_host, o.d_dig, n * 32, filler.reg.get(), "digest");
-    if (!r && hi > lo) r = copy_out(sums_host + lo, o.d_sums + lo, (hi - lo) * 4, filler.reg.get(), "sums");
-    if (host_th.joinable()) host_th.join();
-    for (size_t q = 0; !r && q < host.size(); ++q) {
-        memcpy(digests_host + 32 * (size_t)host[q], &host_dig[32 * q], 32);
-        if (host_sums_off[q + 1] > host_sums_off[q])
-            memcpy(sums_host + soff[host[q]], &host_sums[host_sums_off[q]], (host_sums_off[q + 1] - host_sums_off[q]) * 4);
-    }
-    st.host_blobs = host.size();
-    t_last_call = st;
-    return r;
+    setup_mem_filler(filler, blobs, n, c.on_host, D);
+    return c.run(D, filler, &filler, 64, live_cap_for(D));
 }
 
 // Whole-blob SHA-256 of host buffers (the Digester over many uploads at once): the same
@@ -779,60 +821,19 @@ int krk_sha256_host(const uint8_t* const* data_host, const uint64_t* lengths, ui
     for (uint64_t i = 0; i < n; ++i)
         KRK_CHECK(lengths[i] == 0 || data_host[i], KRK_EINVAL, "blob %llu: data is NULL", (unsigned long long)i);
     std::vector<krk_blob> blobs(n);
-    std::vector<int64_t> plens(n, 1);
-    std::vector<uint64_t> soff(n, 0);
     for (uint64_t i = 0; i < n; ++i) blobs[i] = krk_blob{data_host[i], lengths[i], 1, 0};
-    std::vector<char> on_host(n, 0);
-    std::vector<uint32_t> host;
-    const int off_t = offload_threads(kOffHostSha);
-    if (off_t > 0) {
-        host = offload_plan(lengths, n, off_t, planner_rates(D), nullptr, nullptr, kOffHostSha);
-        for (uint32_t i : host) on_host[i] = 1;
-    }
-    uint8_t* d_dig = nullptr;
-    uint32_t* d_state = nullptr;
-    DevMem mem;
-    KRK_HIP(mem.alloc(&d_dig, n * 32));
-    KRK_HIP(mem.alloc(&d_state, n * 32));
-    std::vector<uint8_t> host_dig(32 * host.size());
-    std::thread host_th;
-    if (!host.empty())
-        host_th = std::thread([&] {
-            std::vector<const uint8_t*> p(host.size());
-            std::vector<uint64_t> l(host.size());
-            for (size_t j = 0; j < host.size(); ++j) {
-                p[j] = data_host[host[j]];
-                l[j] = lengths[host[j]];
-            }
-            offload_hash_host(p, l, off_t, host_dig.data());
-        });
-    struct Joiner {
-        std::thread& t;
-        ~Joiner() {
-            if (t.joinable()) t.join();
-        }
-    } joiner{host_th};
-    struct ShareGuard {
-        int saved;
-        ~ShareGuard() { t_host_share = saved; }
-    } share_guard{t_host_share};
-    if (!host.empty()) t_host_share = std::max(4, host_threads_for_call() - off_t);
+    WindowCall c("sha256_host", blobs.data(), n, nullptr, digests_host, /*crc=*/false);
+    int r = c.plan(D, kOffHostSha, offload_threads(kOffHostSha));
+    if (r) return r;
+    c.start([&](auto& l, auto&, auto&) {
+        std::vector<const uint8_t*> p;
+        for (uint32_t i : c.host) p.push_back(data_host[i]);
+        offload_hash_host(p, l, c.off_t, c.host_dig.data());
+        return KRK_OK;
+    });
     MemFiller filler(blobs.data());
-    setup_mem_filler(filler, blobs.data(), n, on_host, D);
-    CallStats st;
-    int r = windows_pass(D, n, lengths, plens.data(), soff.data(), on_host, filler, 64, live_cap_for(D), nullptr,
-                         d_dig, d_state, &st, /*crc=*/false);
-    if (!r && (hipStreamSynchronize(D->s_a) != hipSuccess || hipStreamSynchronize(D->s_main) != hipSuccess)) {
-        set_error(KRK_EHIP, "sha256_host: sync failed");
-        r = KRK_EHIP;
-    }
-    release_caller_pages(filler, &st);
-    if (!r) r = copy_out(digests_host, d_dig, n * 32, filler.reg.get(), "digest");
-    if (host_th.joinable()) host_th.join();
-    for (size_t q = 0; !r && q < host.size(); ++q) memcpy(digests_host + 32 * (size_t)host[q], &host_dig[32 * q], 32);
-    st.host_blobs = host.size();
-    t_last_call = st;
-    return r;
+    setup_mem_filler(filler, blobs.data(), n, c.on_host, D);
+    return c.run(D, filler, &filler, 64, live_cap_for(D));
 }
 
 // The page-cache resident share of a file batch, from up to 64 evenly spaced files' first
@@ -864,24 +865,13 @@ int krk_metainfo_digest_files(const krk_file_blob* files, uint64_t n, uint32_t* 
     KRK_DEVICE(D);
     if (!n) return KRK_OK;
     KRK_CHECK(files && digests_host, KRK_EINVAL, "metainfo_digest_files: null argument");
-    std::vector<uint64_t> lens(n), soff(n);
-    std::vector<int64_t> plens(n);
-    uint64_t lo = UINT64_MAX, hi = 0;
-    for (uint64_t i = 0; i < n; ++i) {
+    int r = KRK_OK;
+    for (uint64_t i = 0; i < n && !r; ++i) {
         KRK_CHECK(files[i].path, KRK_EINVAL, "file %llu: path is NULL", (unsigned long long)i);
-        KRK_CHECK(files[i].piece_length > 0, KRK_EINVAL, "piece length must be positive");
-        lens[i] = files[i].length;
-        plens[i] = files[i].piece_length;
-        soff[i] = files[i].sums_offset;
-        const uint64_t np = krk_num_pieces(lens[i], plens[i]);
-        KRK_CHECK(soff[i] + np <= 0xFFFFFFFFull, KRK_EINVAL, "sums index exceeds 2^32 in one call");
-        if (np) {
-            lo = std::min(lo, soff[i]);
-            hi = std::max(hi, soff[i] + np);
-        }
+        r = validate_pieces(files[i]);
     }
-    if (lo > hi) lo = hi = 0;
-    KRK_CHECK(hi == lo || sums_host, KRK_EINVAL, "sums_host is NULL");
+    if (r) return r;
+    WindowCall c("metainfo_digest_files", files, n, sums_host, digests_host);
     // Host offload (AUTO by default): the planner's files are read, hashed and piece-summed
     // by host threads in one pass each and never cross the host link.
     // A batch mostly out of the page cache (the residency sample) is bound by the disk,
@@ -889,96 +879,29 @@ int krk_metainfo_digest_files(const krk_file_blob* files, uint64_t n, uint32_t* 
     // take CPU from the window readers (cold 32 GiB leg: AUTO 13.4 GB/s against 14.8
     // GPU-only, profiles/r05/bench_files.json), so such a batch stays on the windows -- and
     // is read with O_DIRECT (below).
-    std::vector<char> on_host(n, 0);
-    std::vector<uint32_t> host;
     int off_t = offload_threads(kOffHostWhole);
-    const double resident = files_resident_fraction(files, n);
-    const bool cold = resident >= 0 && resident < 0.5;
+    c.resident = files_resident_fraction(files, n);
+    const bool cold = c.resident >= 0 && c.resident < 0.5;
     if (cold && offload_auto()) off_t = 0;
-    if (off_t > 0) {
-        host = offload_plan(lens.data(), n, off_t, planner_rates(D), nullptr, nullptr, kOffHostFiles);
-        for (uint32_t i : host) on_host[i] = 1;
-    }
-    Outputs o;
-    int r = o.alloc(n, hi);
+    r = c.plan(D, kOffHostFiles, off_t);
     if (r) return r;
-    std::vector<uint8_t> host_dig(32 * host.size());
-    std::vector<uint64_t> host_sums_off(host.size() + 1, 0);
-    for (size_t j = 0; j < host.size(); ++j)
-        host_sums_off[j + 1] = host_sums_off[j] + krk_num_pieces(lens[host[j]], plens[host[j]]);
-    std::vector<uint32_t> host_sums(host_sums_off.back());
-    int host_rc = KRK_OK;
-    std::string host_err;
-    std::thread host_th;
-    if (!host.empty())
-        host_th = std::thread([&] {
-            std::vector<const char*> p(host.size());
-            std::vector<uint64_t> l(host.size()), pl(host.size());
-            std::vector<uint32_t*> so(host.size());
-            for (size_t j = 0; j < host.size(); ++j) {
-                p[j] = files[host[j]].path;
-                l[j] = lens[host[j]];
-                pl[j] = (uint64_t)plens[host[j]];
-                so[j] = host_sums.data() + host_sums_off[j];
-            }
-            host_rc = offload_whole_files(p, l, pl, so, off_t, host_dig.data());
-            if (host_rc) host_err = t_err;
-        });
-    struct Joiner {
-        std::thread& t;
-        ~Joiner() {
-            if (t.joinable()) t.join();
-        }
-    } joiner{host_th};
-    struct ShareGuard {
-        int saved;
-        ~ShareGuard() { t_host_share = saved; }
-    } share_guard{t_host_share};
-    if (!host.empty()) t_host_share = std::max(4, host_threads_for_call() - off_t);
+    c.start([&](auto& l, auto& pl, auto& so) {
+        std::vector<const char*> p;
+        for (uint32_t i : c.host) p.push_back(files[i].path);
+        return offload_whole_files(p, l, pl, so, c.off_t, c.host_dig.data());
+    });
     // O_DIRECT reads (Linux AIO, a window's chunks queued at once): KRK_FILE_DIRECT=1 / 0
     // force them on / off; by default a cold batch takes them (no page-cache copy, a deep
     // disk queue from one thread: 16.3 GB/s against 11.7 for 16 threads' page-cache preads
     // of the same window chunks, profiles/r05/disk_probe_aio.jsonl) and a cached one reads
     // the page cache.
     const char* fd_env = KRK_OP_ENV("KRK_FILE_DIRECT");
-    const bool direct = fd_env ? atoi(fd_env) > 0 : cold;
+    const bool direct = c.direct_reads = fd_env ? atoi(fd_env) > 0 : cold;
     FileFiller filler(files, n, direct);
-    CallStats st;
     // at most as many live blobs as this call holds file descriptors (a lease of the
     // process's budget, shared with every other file batch running now)
     FdLease fds(std::min<uint64_t>(direct ? direct_live_cap(D) : live_cap_for(D), n));
-    r = windows_pass(D, n, lens.data(), plens.data(), soff.data(), on_host, filler, direct ? 4096 : 64, fds.n,
-                     o.d_sums, o.d_dig, o.d_state, &st);
-    st.resident = resident;
-    st.direct_reads = direct;
-    // drain what was queued even after a read error (the windows' kernels read the buffers)
-    const bool synced = hipStreamSynchronize(D->s_a) == hipSuccess && hipStreamSynchronize(D->s_b) == hipSuccess &&
-                        hipStreamSynchronize(D->s_main) == hipSuccess;
-    if (!r && !synced) {
-        set_error(KRK_EHIP, "metainfo_digest_files: sync failed");
-        r = KRK_EHIP;
-    }
-    if (!r && hipMemcpy(digests_host, o.d_dig, n * 32, hipMemcpyDeviceToHost) != hipSuccess) {
-        set_error(KRK_EHIP, "digest copy-out failed");
-        r = KRK_EHIP;
-    }
-    if (!r && hi > lo && hipMemcpy(sums_host + lo, o.d_sums + lo, (hi - lo) * 4, hipMemcpyDeviceToHost) != hipSuccess) {
-        set_error(KRK_EHIP, "sums copy-out failed");
-        r = KRK_EHIP;
-    }
-    if (host_th.joinable()) host_th.join();
-    if (!r && host_rc) {
-        t_err = host_err;
-        r = host_rc;
-    }
-    for (size_t q = 0; !r && q < host.size(); ++q) {
-        memcpy(digests_host + 32 * (size_t)host[q], &host_dig[32 * q], 32);
-        if (host_sums_off[q + 1] > host_sums_off[q])
-            memcpy(sums_host + soff[host[q]], &host_sums[host_sums_off[q]], (host_sums_off[q + 1] - host_sums_off[q]) * 4);
-    }
-    st.host_blobs = host.size();
-    t_last_call = st;
-    return r;
+    return c.run(D, filler, nullptr, direct ? 4096 : 64, fds.n);
 }
 
 int krk_windows_last_call(uint64_t* max_live, int* windows, uint64_t* host_blobs) {

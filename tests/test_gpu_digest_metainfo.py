@@ -606,3 +606,83 @@ def test_host_whole_offload_piece_lengths(gpu, orc):
                 assert np.array_equal(sums[i], orc.calc_piece_sums(d, P)[1]), (P, i)
     finally:
         D.set_sha_host_offload(0)
+
+
+def _window_entry_points(datas, paths, P, sums_null=False):
+    """(name, rc, sums or None, digests) of krk_metainfo_digest_host, krk_sha256_host and
+    krk_metainfo_digest_files over the same blobs (raw ctypes; sums_null: sums_host = NULL)."""
+    from kraken_amd._capi import krk_blob, krk_file_blob
+    n = len(datas)
+    counts = [int(lib.krk_num_pieces(int(d.size), P)) for d in datas]
+    offs = np.concatenate([[0], np.cumsum(counts)]).astype(np.uint64)
+    u32p, u8p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)
+    blobs = (krk_blob * n)(*[krk_blob(d.ctypes.data if d.size else None, int(d.size), P, int(offs[i]))
+                             for i, d in enumerate(datas)])
+    enc = [p.encode() for p in paths]  # kept alive for the call
+    files = (krk_file_blob * n)(*[krk_file_blob(enc[i], int(d.size), P, int(offs[i])) for i, d in enumerate(datas)])
+    ptrs = (C.c_void_p * n)(*[d.ctypes.data if d.size else None for d in datas])
+    lens = np.array([d.size for d in datas], dtype=np.uint64)
+    for name in ("metainfo_digest_host", "sha256_host", "metainfo_digest_files"):
+        sums = None if sums_null or name == "sha256_host" else np.zeros(max(int(offs[-1]), 1), dtype=np.uint32)
+        dg = np.zeros((n, 32), dtype=np.uint8)
+        sp = sums.ctypes.data_as(u32p) if sums is not None else None
+        if name == "sha256_host":
+            rc = lib.krk_sha256_host(ptrs, lens.ctypes.data_as(C.POINTER(C.c_uint64)), n, dg.ctypes.data_as(u8p))
+        else:
+            arr = blobs if name == "metainfo_digest_host" else files
+            rc = getattr(lib, "krk_" + name)(arr, n, sp, dg.ctypes.data_as(u8p))
+        yield name, rc, None if sums is None else [sums[int(offs[i]):int(offs[i + 1])] for i in range(n)], dg
+
+
+def _write_blobs(tmp_path, datas):
+    paths = []
+    for i, d in enumerate(datas):
+        paths.append(str(tmp_path / f"w{i}"))
+        with open(paths[-1], "wb") as f:
+            f.write(memoryview(d))
+    return paths
+
+
+def test_window_entry_points_host_takes_whole_batch(gpu, orc, tmp_path):
+    """Every blob on the host offload (the planner's choice with these rates, checked first):
+    the three host-resident entry points run no window at all -- the window pass returns
+    before it leases staging -- and digests and sums are the host share's, equal to hashlib
+    and the oracle."""
+    P = 1 << 20
+    sizes = [2 << 20, (1 << 20) + 1]
+    datas = [orc.synth(80 + i, L) for i, L in enumerate(sizes)]
+    paths = _write_blobs(tmp_path, datas)
+    D.set_sha_host_offload(8)
+    D.set_planner_rates(dict(D.planner_rates(), sha_stream_bps=[1e6, 1e6, 1e6]))  # the host takes all
+    try:
+        for mode in (D.OFFLOAD_HOST_SHA, D.OFFLOAD_HOST_WHOLE, D.OFFLOAD_HOST_FILES):
+            assert sorted(D.sha_offload_plan(sizes, 8, mode=mode)[0].tolist()) == [0, 1], mode
+        got = []
+        for name, rc, sums, dg in _window_entry_points(datas, paths, P):
+            check(rc)
+            got.append((name, sums, dg, D.windows_last_call()))
+    finally:
+        D.set_sha_host_offload(0)
+        D.set_planner_rates(None)
+    assert [g[0] for g in got] == ["metainfo_digest_host", "sha256_host", "metainfo_digest_files"]
+    for name, sums, dg, st in got:
+        assert st["windows"] == 0 and st["host_blobs"] == 2, (name, st)
+        for i, d in enumerate(datas):
+            assert bytes(dg[i]) == hashlib.sha256(d.tobytes()).digest(), (name, i)
+            if sums is not None:
+                assert np.array_equal(sums[i], orc.calc_piece_sums(d, P)[1]), (name, i)
+
+
+def test_window_entry_points_no_pieces_null_sums(gpu, tmp_path):
+    """Three empty blobs (for the files call three existing empty files) and sums_host = NULL:
+    no piece exists, so no sums array is needed; KRK_OK and every digest sha256(b"")."""
+    datas = [np.zeros(0, dtype=np.uint8) for _ in range(3)]
+    paths = _write_blobs(tmp_path, datas)
+    names = []
+    for name, rc, sums, dg in _window_entry_points(datas, paths, 1 << 20, sums_null=True):
+        check(rc)
+        names.append(name)
+        assert sums is None
+        for i in range(3):
+            assert bytes(dg[i]) == hashlib.sha256(b"").digest(), (name, i)
+    assert names == ["metainfo_digest_host", "sha256_host", "metainfo_digest_files"]

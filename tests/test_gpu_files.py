@@ -165,6 +165,33 @@ def test_files_errors_keep_reference_texts(gpu, orc, tmp_path, mode, monkeypatch
     assert bytes(dg[0]) == hashlib.sha256(d.tobytes()).digest()
 
 
+def test_files_host_offloaded_failure_reaches_caller(gpu, orc, tmp_path):
+    """A file the planner gives to the host offload and that turns out shorter than declared:
+    the host thread's KRK_EIO and its text come back from krk_metainfo_digest_files, the call's
+    stats still count the host blob, and the same file with its true length then succeeds."""
+    P = 1 << 20
+    d = orc.synth(61, 1 << 20)
+    p = _write(tmp_path, "short_host", d)
+    D.set_sha_host_offload(8)
+    D.set_planner_rates(dict(D.planner_rates(), sha_stream_bps=[1e6, 1e6, 1e6]))  # the host takes files
+    try:
+        for L in ((1 << 20) + 10, 1 << 20):
+            assert D.sha_offload_plan([L], 8, mode=D.OFFLOAD_HOST_FILES)[0].tolist() == [0]
+        with pytest.raises(KrakenError) as e:
+            D.metainfo_digest_files([p], [(1 << 20) + 10], P)  # stat said longer: EOF
+        bad = D.windows_last_call()
+        sums, dg = D.metainfo_digest_files([p], [1 << 20], P)
+        good = D.windows_last_call()
+    finally:
+        D.set_sha_host_offload(0)
+        D.set_planner_rates(None)
+    assert e.value.code == KRK_EIO and str(e.value).endswith(f"read blob: {p}: unexpected EOF"), str(e.value)
+    assert bad["host_blobs"] == 1, bad
+    assert good["host_blobs"] == 1, good
+    assert bytes(dg[0]) == hashlib.sha256(d.tobytes()).digest()
+    assert np.array_equal(sums[0], orc.calc_piece_sums(d, P)[1])
+
+
 def test_files_multi_equals_single(gpu, orc, tmp_path):
     lens = [int(x) for x in np.random.default_rng(5).integers(0, 6 << 20, 40)]
     datas = [orc.synth(900 + i, L) for i, L in enumerate(lens)]
