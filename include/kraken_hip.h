@@ -342,7 +342,9 @@ int krk_info_hash(int64_t piece_length, const uint32_t* sums, uint64_t n_sums,
  * copied to sums_host at blobs[i].sums_offset) and its InfoHash (info_hash20, 20 B a
  * blob; names/name_off = the blobs' digest hex, the info Name).  The batch runs as up to
  * 8 groups of about equal bytes back to back on `stream`; each group's sums are copied
- * back and hashed on host threads while the later groups' kernels run.  Synchronous. */
+ * back and hashed on host threads while the later groups' kernels run.  Synchronous.
+ * With the InfoHash placed on the device (krk_set_info_hash_placement below) the hashes come
+ * from krk_info_hash_batch_dev's kernel instead and no host thread is started. */
 int krk_metainfo_batch_dev(const krk_blob* blobs, uint64_t n_blobs, const char* names, const uint64_t* name_off,
                            uint32_t* sums_dev, uint32_t* sums_host, uint8_t* info_hash20, void* stream);
 int krk_info_hash_batch(const int64_t* piece_lengths, const uint32_t* sums, const uint64_t* sums_off,
@@ -351,6 +353,26 @@ int krk_info_hash_batch(const int64_t* piece_lengths, const uint32_t* sums, cons
 int krk_bencode_info(int64_t piece_length, const uint32_t* sums, uint64_t n_sums,
                      const char* name, uint64_t name_len, int64_t length,
                      uint8_t* out, uint64_t cap, uint64_t* written);
+/* krk_info_hash_batch on the device, from piece sums already in device memory: the same
+ * arguments and the same 20 bytes a blob, with sums_dev device memory and out20 device memory
+ * or page-locked host memory (krk_host_alloc; as krk_ring_locations_dev: any other pointer is
+ * KRK_EINVAL).  One wave a blob formats the bencoding into an on-chip ring and hashes it from
+ * there; the text never exists in memory.  Asynchronous on `stream`: every host array (names
+ * included) is copied into the library's staging before the call returns, so the caller may
+ * overwrite them at once; out20 is valid once the stream reaches the call's end.  names may be
+ * NULL when every name is empty; n == 0 is KRK_OK; KRK_ENODEV without a gfx950 device. */
+int krk_info_hash_batch_dev(const int64_t* piece_lengths, const uint32_t* sums_dev, const uint64_t* sums_off,
+                            const uint64_t* n_sums, const char* names, const uint64_t* name_off,
+                            const int64_t* lengths, uint64_t n, uint8_t* out20, void* stream);
+/* Where krk_metainfo_batch_dev (and nothing else) computes its InfoHashes, process-wide:
+ * KRK_PLACE_HOST (each group's sums copied back and hashed on host threads while later
+ * groups' kernels run), KRK_PLACE_GPU (krk_info_hash_batch_dev's kernel behind the piece-sum
+ * launches on the library's streams; the sums and the hashes copied back once, no host thread
+ * started) or KRK_PLACE_AUTO, the default, which for now means KRK_PLACE_HOST.  The
+ * environment variable KRK_INFOHASH_PLACEMENT (0/1/2), read once, sets the same; a call wins
+ * over it.  Another value is KRK_EINVAL.  krk_info_hash_placement reports the setting. */
+int krk_set_info_hash_placement(int placement);
+int krk_info_hash_placement(int* placement);
 
 /* pieceLengthConfig.get (lib/metainfogen/config.go:71-80); thresholds ascending. */
 int64_t krk_piece_length_for_size(const int64_t* thresholds, const int64_t* lengths,

@@ -153,6 +153,17 @@ int krk_set_host_gather(int mode);
 int krk_host_sha256(const uint8_t* data, uint64_t n, uint8_t out32[32]);
 int krk_host_crc32_update(uint32_t crc, const uint8_t* data, uint64_t n, uint32_t* out);
 
+/* ------------------------------------------------------- device InfoHash
+ * One InfoHash on the calling thread through the device kernel's own arithmetic
+ * (csrc/info_hash_math.hpp: digit count and emit by multiply-high, the header builder, the
+ * byte ring, the padding and the SHA-1 block function), its 64-lane steps run one lane after
+ * another.  Arguments and result as krk_info_hash; no device needed. */
+int krk_info_hash_math_host(int64_t piece_length, const uint32_t* sums, uint64_t n_sums, const char* name,
+                            uint64_t name_len, int64_t length, uint8_t out20[20]);
+/* Where the calling thread's last krk_metainfo_batch_dev computed its InfoHashes:
+ * KRK_PLACE_HOST or KRK_PLACE_GPU (krk_set_info_hash_placement, resolved). */
+int krk_metainfo_batch_last_placement(int* placement);
+
 /* ----------------------------------------------------- synthetic blobs
  * Fills a device buffer with bytes [offset, offset+n) of synthetic blob
  * blob_idx (splitmix64 counter stream, variant 0 = uniform bytes, 1 = alnum;
@@ -175,7 +186,7 @@ int krk_device_cus(int* out);
  * When enabled, every kernel launch is bracketed by hipEvents recorded on the stream
  * the kernel runs on; krk_kernel_stats returns the number of launches and their summed
  * device time (ms) since the last reset for kernel name "crc32_pieces", "sha256_multi",
- * "hrw_shard_table", "hrw_gather" or "synth_fill" (timed launches are synchronised
+ * "hrw_shard_table", "hrw_gather", "synth_fill" or "info_hash" (timed launches are synchronised
  * lazily). */
 int krk_set_timing(int on);
 /* Shader clock of the calling thread's device, measured by a one-wave probe kernel on

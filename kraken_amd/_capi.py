@@ -149,6 +149,11 @@ def _load() -> C.CDLL:
                                     C.c_uint64, u8p]),
         "krk_bencode_info": (i, [C.c_int64, u32p, C.c_uint64, C.c_char_p, C.c_uint64, C.c_int64, u8p,
                                  C.c_uint64, u64p]),
+        "krk_info_hash_batch_dev": (i, [i64p, vp, u64p, u64p, C.c_char_p, u64p, i64p, C.c_uint64, vp, vp]),
+        "krk_set_info_hash_placement": (i, [i]),
+        "krk_info_hash_placement": (i, [C.POINTER(C.c_int)]),
+        "krk_info_hash_math_host": (i, [C.c_int64, u32p, C.c_uint64, C.c_char_p, C.c_uint64, C.c_int64, u8p]),
+        "krk_metainfo_batch_last_placement": (i, [C.POINTER(C.c_int)]),
         "krk_piece_length_for_size": (C.c_int64, [i64p, i64p, C.c_uint32, C.c_int64]),
         "krk_hrw_ordered": (i, [C.c_char_p, u64p, C.c_uint64, nodesp, C.c_uint32, i32p, f64p]),
         "krk_ring_locations": (i, [u8p, C.c_uint64, nodesp, u8p, C.c_int32, i32p, u8p]),

@@ -191,6 +191,84 @@ int krk_sha256_dev_on_host(const uint8_t* const* data_dev, const uint64_t* lengt
     return offload_hash(D, p, l, threads > 0 ? threads : host_threads_for_call(), ready, digests_host);
 }
 
+static thread_local int t_last_ih_place = KRK_PLACE_HOST;  // krk_metainfo_batch_last_placement
+
+int krk_metainfo_batch_last_placement(int* placement) {
+    KRK_CHECK(placement, KRK_EINVAL, "metainfo_batch_last_placement: null argument");
+    *placement = t_last_ih_place;
+    return KRK_OK;
+}
+
+// krk_metainfo_batch_dev with the InfoHash on the device (krk_set_info_hash_placement): the
+// CRC launches on D->s_a, the InfoHash launches (info_hash.hip) on D->s_b, group g's InfoHash
+// after group g's CRC by an event and beside group g+1's CRC; both forked from and joined
+// back into s, where the sums and the hashes are copied back once.  No host thread is started.
+// One group (KRK_INFOHASH_GROUPS): a second CRC launch's ramp and tail cost about what the
+// InfoHash launch it would hide takes (C5 regen: 0.22 ms).  C5 regen 9.45 / 9.49 ms a step with
+// one group, 9.45 / 9.27 with two, 9.92 / 9.85 with four; the host placement 9.21-9.45
+// (profiles/r07/infohash_dev.json).
+static int metainfo_batch_gpu(Device* D, const krk_blob* blobs, uint64_t n, const char* names,
+                              const uint64_t* name_off, uint32_t* sums_dev, uint32_t* sums_host, uint8_t* info_hash20,
+                              hipStream_t s, const int64_t* pl, const int64_t* ln, const uint64_t* so,
+                              const uint64_t* ns, uint64_t total) {
+    static const uint64_t kGroups = [] {
+        const char* g = KRK_AB_ENV("KRK_INFOHASH_GROUPS");
+        return (uint64_t)std::max(1, g ? atoi(g) : 1);
+    }();
+    const uint64_t G = std::min<uint64_t>(n, kGroups);
+    std::vector<uint64_t> cut{0};
+    for (uint64_t i = 0, acc = 0; i < n && cut.size() < G; ++i) {
+        acc += blobs[i].length;
+        if ((double)acc * (double)G >= (double)total * (double)cut.size() && i + 1 < n) cut.push_back(i + 1);
+    }
+    cut.push_back(n);
+    const size_t ng = cut.size() - 1;
+    uint8_t* d_ih = nullptr;
+    KRK_HIP(scratch_alloc(D, &d_ih, 20 * n, s));
+    Event fork, join;
+    std::vector<Event> ev(ng);
+    int r = KRK_OK;
+    auto hip = [&r](hipError_t e, const char* what) {
+        if (e != hipSuccess && !r) {
+            set_error(KRK_EHIP, "metainfo_batch_dev: %s: %s", what, hipGetErrorString(e));
+            r = KRK_EHIP;
+        }
+        return e == hipSuccess;
+    };
+    bool forked = hip(fork.create(), "event create") && hip(join.create(), "event create") &&
+                  hip(hipEventRecord(fork, s), "event record") && hip(hipStreamWaitEvent(D->s_a, fork, 0), "fork") &&
+                  hip(hipStreamWaitEvent(D->s_b, fork, 0), "fork");
+    for (size_t g = 0; forked && g < ng && !r; ++g) {
+        const uint64_t a = cut[g], m = cut[g + 1] - cut[g];
+        if (!hip(ev[g].create(), "event create")) break;
+        r = piece_sums_dev(D, blobs + a, m, sums_dev, D->s_a);
+        if (r || !hip(hipEventRecord(ev[g], D->s_a), "event record") ||
+            !hip(hipStreamWaitEvent(D->s_b, ev[g], 0), "event wait"))
+            break;
+        r = info_hash_dev(D, pl + a, sums_dev, so + a, ns + a, names, name_off + a, ln + a, m, d_ih + 20 * a, D->s_b);
+    }
+    if (forked) {  // s follows everything queued on the two streams, failed batch or not
+        hip(hipEventRecord(join, D->s_a), "event record");
+        hip(hipStreamWaitEvent(s, join, 0), "join");
+        Event join_b;
+        if (hip(join_b.create(), "event create") && hip(hipEventRecord(join_b, D->s_b), "event record"))
+            hip(hipStreamWaitEvent(s, join_b, 0), "join");
+        if (r) {  // an event was missing somewhere: wait for the streams themselves
+            hipStreamSynchronize(D->s_a);
+            hipStreamSynchronize(D->s_b);
+        }
+    }
+    if (!r) {
+        uint64_t lo, hi;
+        sums_span(blobs, n, &lo, &hi);
+        if (hi > lo) hip(hipMemcpyAsync(sums_host + lo, sums_dev + lo, (hi - lo) * 4, hipMemcpyDeviceToHost, s), "sums copy");
+        hip(hipMemcpyAsync(info_hash20, d_ih, 20 * n, hipMemcpyDeviceToHost, s), "hash copy");
+    }
+    hip(hipStreamSynchronize(s), "sync");
+    scratch_free(D, d_ih, s);
+    return r;
+}
+
 int krk_metainfo_batch_dev(const krk_blob* blobs, uint64_t n_blobs, const char* names, const uint64_t* name_off,
                            uint32_t* sums_dev, uint32_t* sums_host, uint8_t* info_hash20, void* stream) {
     KRK_DEVICE(D);
@@ -211,6 +289,10 @@ int krk_metainfo_batch_dev(const krk_blob* blobs, uint64_t n_blobs, const char* 
         ns[i] = krk_num_pieces(blobs[i].length, blobs[i].piece_length);
         total += blobs[i].length;
     }
+    t_last_ih_place = info_hash_placement_resolved();
+    if (t_last_ih_place == KRK_PLACE_GPU)
+        return metainfo_batch_gpu(D, blobs, n_blobs, names, name_off, sums_dev, sums_host, info_hash20, s, pl.data(),
+                                  ln.data(), so.data(), ns.data(), total);
     // Four groups (KRK_REGEN_GROUPS): C5 regen 9.84-9.90 ms a step against 10.14-10.16
     // with eight (each launch's ramp and tail cost more than the InfoHash overlap buys) and
     // 9.70-10.07 with one (profiles/r03/regen_groups_ab.txt).

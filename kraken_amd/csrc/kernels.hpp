@@ -145,6 +145,24 @@ hipError_t launch_sha256_plan(int plan, const ShaJob* jobs, uint32_t n_jobs, uin
 bool sha_plan_valid(int plan);
 void set_sha_plan(int plan);
 
+// ---------------------------------------------------------------- InfoHash
+// One job = one blob's info.Hash() (info_hash.hip), run by one wave: SHA-1 over the bencoded
+// info{length, names[name_off, +name_len), piece_length, sums[first_sum, +n_sums)}, the 20
+// digest bytes to out20 + 20 * out.
+struct alignas(16) InfoHashJob {
+    int64_t piece_length;
+    int64_t length;
+    uint64_t first_sum;
+    uint64_t n_sums;
+    uint64_t name_off;
+    uint64_t name_len;
+    uint64_t out;
+    uint64_t pad;
+};
+static_assert(sizeof(InfoHashJob) == 64, "InfoHashJob layout");
+hipError_t launch_info_hash(const InfoHashJob* jobs, uint32_t n_jobs, const uint32_t* sums, const uint8_t* names,
+                            uint8_t* out20, hipStream_t s);
+
 // ---------------------------------------------------------------- host gather
 // One tile of a host -> device gather (gather.hip): n <= kGatherTile bytes from src (a
 // device-visible address of page-locked host memory: a hipHostMalloc'd or registered

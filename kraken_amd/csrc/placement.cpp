@@ -405,7 +405,7 @@ static void owner_used(Device* D, size_t slot, hipStream_t s) {
 // memory the GPU maps at its host address (krk_host_alloc / hipHostMalloc / registered:
 // the gather then writes the owner lists over PCIe and the caller needs no copy-back).
 // Pageable memory, or a mapping at another address, is refused -- the kernel would fault.
-static bool device_writable(const void* p, uint64_t n) {
+bool krk::device_writable(const void* p, uint64_t n) {
     auto ok_at = [](const void* q) {
         hipPointerAttribute_t a{};
         if (hipPointerGetAttributes(&a, q) != hipSuccess) {

@@ -1,6 +1,6 @@
 // runtime.hpp -- internal to libkraken_hip: device contexts, the stream-ordered
 // scratch cache, the CRC work builder and the SHA job runner shared by the C ABI
-// (runtime.cpp, batch_dev.cpp, crc_host.cpp, placement.cpp, windows.cpp) and the
+// (runtime.cpp, batch_dev.cpp, info_hash_dev.cpp, crc_host.cpp, placement.cpp, windows.cpp) and the
 // submission engine (engine.cpp).  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -72,9 +72,9 @@ struct Event {
 };
 
 // ------------------------------------------------------------------ timing
-enum Kern { K_CRC, K_SHA, K_HRW, K_FILTER, K_GATHER, K_SYNTH, K_HOSTG, K_N };
+enum Kern { K_CRC, K_SHA, K_HRW, K_FILTER, K_GATHER, K_SYNTH, K_HOSTG, K_INFOHASH, K_N };
 inline const char* kKernNames[K_N] = {"crc32_pieces", "sha256_multi", "hrw_order",   "ring_filter",
-                                      "hrw_gather",   "synth_fill",   "host_gather"};
+                                      "hrw_gather",   "synth_fill",   "host_gather", "info_hash"};
 inline std::atomic<bool> g_timing{false};
 struct Pending {
     hipEvent_t a, b;
@@ -858,6 +858,18 @@ struct TailSrc {
     const uint64_t* start;
     hipEvent_t gpu_done;
 };
+// Where a kernel may write [p, p + n): device memory, or page-locked host memory the GPU maps
+// at its host address (placement.cpp).
+bool device_writable(const void* p, uint64_t n);
+// InfoHashes of n blobs from piece sums in device memory (info_hash_dev.cpp): the arguments of
+// krk_info_hash_batch with sums_dev and out20 device-visible; every host array is staged
+// before it returns, the launch is queued on s.
+int info_hash_dev(Device* D, const int64_t* piece_lengths, const uint32_t* sums_dev, const uint64_t* sums_off,
+                  const uint64_t* n_sums, const char* names, const uint64_t* name_off, const int64_t* lengths,
+                  uint64_t n, uint8_t* out20, hipStream_t s);
+// What KRK_PLACE_AUTO resolves to for krk_metainfo_batch_dev's InfoHash (info_hash_dev.cpp):
+// KRK_PLACE_HOST or KRK_PLACE_GPU.
+int info_hash_placement_resolved();
 void owner_tables_teardown(Device& D);  // krk_shutdown: the cached owner tables (placement.cpp)
 void offload_teardown(Device& D);  // krk_shutdown: the offload threads' streams and pinned buffers
 void offload_hash_host(const std::vector<const uint8_t*>& ptrs, const std::vector<uint64_t>& lens, int threads,

@@ -202,7 +202,8 @@ def pack_names(names):
 def metainfo_batch(arena: BlobArena, out: BatchOutputs, names, sums_host: np.ndarray, stream=None) -> np.ndarray:
     """Generator.Generate over the arena's blobs (krk_metainfo_batch_dev): piece sums into
     out.sums and sums_host (uint32, arena layout) and the InfoHashes, returned as an
-    (n, 20) uint8 array; the host hashes each group while later groups' kernels run.
+    (n, 20) uint8 array; the host hashes each group while later groups' kernels run, or the
+    device kernel does under set_info_hash_placement(KRK_PLACE_GPU).
     names: the blobs' names (str), or pack_names() of them."""
     n = len(arena.lengths)
     buf, noff = names if isinstance(names, tuple) else pack_names(names)
@@ -215,6 +216,55 @@ def metainfo_batch(arena: BlobArena, out: BatchOutputs, names, sums_host: np.nda
                                      sums_host.ctypes.data_as(C.POINTER(C.c_uint32)),
                                      ih.ctypes.data_as(C.POINTER(C.c_uint8)), stream))
     return ih[:n]
+
+
+def info_hash_batch_dev(piece_lengths, sums: DeviceBuffer, sums_off, n_sums, names, lengths, out=None, stream=None):
+    """krk_info_hash_batch_dev: the InfoHashes of n blobs from piece sums in device memory
+    (`sums`, uint32; blob i's at sums_off[i] .. + n_sums[i]), computed by the device kernel.
+    names: the blobs' names (str), pack_names() of them, or None when every name is empty.
+    out: a DeviceBuffer or PinnedArray of 20 n bytes to fill, asynchronously on `stream` (it is
+    returned); None: an (n, 20) uint8 array, returned once the stream has run the call."""
+    pl = np.ascontiguousarray(piece_lengths, dtype=np.int64)
+    n = pl.size
+    so = np.ascontiguousarray(sums_off, dtype=np.uint64)
+    ns = np.ascontiguousarray(n_sums, dtype=np.uint64)
+    ln = np.ascontiguousarray(lengths, dtype=np.int64)
+    if not (so.size == ns.size == ln.size == n):
+        raise ValueError("info_hash_batch_dev: the per-blob arrays differ in length")
+    if names is None:
+        buf, noff = b"", np.zeros(n + 1, dtype=np.uint64)
+    else:
+        buf, noff = names if isinstance(names, tuple) else pack_names(names)
+    if noff.size != n + 1:
+        raise ValueError(f"info_hash_batch_dev: {noff.size - 1} names for {n} blobs")
+    dst = PinnedArray((max(n, 1), 20), np.uint8) if out is None else out
+    i64p, u64p = C.POINTER(C.c_int64), C.POINTER(C.c_uint64)
+    check(lib.krk_info_hash_batch_dev(pl.ctypes.data_as(i64p), sums.ptr, so.ctypes.data_as(u64p),
+                                      ns.ctypes.data_as(u64p), buf or None, noff.ctypes.data_as(u64p),
+                                      ln.ctypes.data_as(i64p), n, dst.ptr, stream))
+    if out is not None:
+        return out
+    check(lib.krk_stream_sync(stream))
+    return dst.a[:n].copy()
+
+
+def set_info_hash_placement(placement: int):
+    """krk_set_info_hash_placement: where metainfo_batch computes its InfoHashes, process-wide
+    (KRK_PLACE_AUTO = HOST for now, KRK_PLACE_HOST, KRK_PLACE_GPU)."""
+    check(lib.krk_set_info_hash_placement(int(placement)))
+
+
+def info_hash_placement() -> int:
+    v = C.c_int(-1)
+    check(lib.krk_info_hash_placement(C.byref(v)))
+    return v.value
+
+
+def metainfo_batch_last_placement() -> int:
+    """Where this thread's last metainfo_batch computed its InfoHashes (KRK_PLACE_HOST / _GPU)."""
+    v = C.c_int(-1)
+    check(lib.krk_metainfo_batch_last_placement(C.byref(v)))
+    return v.value
 
 
 def sha256(arena: BlobArena, out: BatchOutputs, stream=None):
