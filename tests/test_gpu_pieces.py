@@ -40,9 +40,9 @@ def test_piece_sums_edge_lengths(gpu, orc, P):
     _check_arena(arena, orc)
 
 
-@pytest.mark.parametrize("misalign", [1, 3, 8])
+@pytest.mark.parametrize("misalign", list(range(1, 16)))
 def test_piece_sums_unaligned(gpu, orc, misalign):
-    lens = [5, 100, 4096 + 5, 70000, 300000]
+    lens = [5, 100, 4096 + 5, 70000, 300000, 63, 64, 65, 4095, 4096, 4097, 262145]
     arena = D.BlobArena(lens, 65536, blob_ids=range(7, 7 + len(lens)), misalign=misalign)
     _check_arena(arena, orc)
 
