@@ -160,6 +160,51 @@ int krk_verify_pieces_dev(const krk_blob* blob, const uint32_t* expected_host,
 int krk_verify_pieces_host(const uint8_t* const* data, const uint64_t* lengths, const uint32_t* expected,
                            uint64_t n, uint8_t* ok_out);
 
+/* ------------------------------------------- verify against stored MetaInfo
+ * Which pieces of a blob still match the MetaInfo stored for it, answered as the reference
+ * answers it: Torrent.Bitfield() (lib/torrent/storage/agentstorage/torrent.go:130-140), a
+ * willf/bitset -- []uint64, piece i is bit (i & 63) of word (i >> 6), 1 = complete; the tail
+ * bits of a blob's last word are 0.  This is the "recheck" of a download file against its
+ * metainfo (the agent keeps complete[] only from what writePiece saw, torrent.go:174-220) and
+ * the read-only scrub of a CAS cache against its _torrentmeta sidecars -- what
+ * Generator.Generate (lib/metainfogen/generator.go:41-58) would compute, compared instead of
+ * written.  For the origin the blob's SHA-256 (core.Digester, core/digester.go:28-72) is also
+ * compared with its name (uploader.verify, origin/blobserver/uploader.go:74-94): the only check
+ * that catches a sidecar regenerated over rotten bytes.
+ *
+ * Bitfield layout of a batch: blob i's krk_bitfield_words(num_pieces) words follow blob i-1's;
+ * blob i's first word index is the running sum of krk_bitfield_words over the earlier blobs (a
+ * blob without pieces owns no word).  n_bad[i] = blob i's mismatching pieces.  Every output
+ * word, count and flag is written by the call; the caller pre-zeroes nothing. */
+uint64_t krk_bitfield_words(uint64_t n_pieces);              /* ceil(n_pieces / 64) */
+/* One blob's bitfield from sums already on the host (the bitset the agent's Bitfield() returns
+ * for them): pure host code, no device; bit-identical to the device kernel.  n_bad_out may be
+ * NULL. */
+int krk_piece_bitfield(const uint32_t* sums, const uint32_t* expected, uint64_t n_pieces,
+                       uint64_t* bits_out, uint32_t* n_bad_out);
+/* Device-resident batch (the batch form of krk_verify_pieces_dev; with digests, of
+ * uploader.verify + Generate compared): blobs[i].data are device pointers; expected_host is
+ * indexed by blobs[i].sums_offset; expected_digests_host is n_blobs*32 bytes, or NULL for the
+ * piece-sum pass alone.  With digests the SHA-256 and CRC kernels run as in
+ * krk_metainfo_digest_dev (two streams joined into `stream`, the host offload as set).  One
+ * wave ballots 64 consecutive pieces of one blob into one word.  bits_out, n_bad_out (n_blobs)
+ * and digest_ok_out (n_blobs bytes, 1 = equal; non-NULL exactly when digests are given) are
+ * device memory or page-locked host memory (krk_host_alloc): any other pointer is KRK_EINVAL
+ * before anything is launched.  Asynchronous on `stream`: every host array is copied into the
+ * library's staging before the call returns; the sums and digests stay in device scratch.
+ * n_blobs == 0 is KRK_OK; KRK_ENODEV without a gfx950 device. */
+int krk_verify_batch_dev(const krk_blob* blobs, uint64_t n_blobs, const uint32_t* expected_host,
+                         const uint8_t* expected_digests_host, uint64_t* bits_out, uint32_t* n_bad_out,
+                         uint8_t* digest_ok_out, void* stream);
+/* The same over cache or download FILES, all arrays on the host.  Synchronous.  Without
+ * digests it is krk_piece_sums_files underneath (the same CRC placement rule; HOST placement
+ * needs no device; krk_crc_host_split reports the call's split); with digests it is
+ * krk_metainfo_digest_files (one read a byte feeds both).  Errors are the underlying call's:
+ * KRK_EIO "read blob: <path>: unexpected EOF", "open <path>: <errno text>". */
+int krk_verify_files(const krk_file_blob* files, uint64_t n_files, const uint32_t* expected,
+                     const uint8_t* expected_digests, uint64_t* bits_host, uint32_t* n_bad_host,
+                     uint8_t* digest_ok_host);
+
 /* ----------------------------------------------------- SHA-256 (Digester)
  * Replaces core.Digester (core/digester.go:28-72): crypto.SHA256 over the whole
  * blob.  One Merkle-Damgard stream per lane, many blobs per launch. */

@@ -95,6 +95,10 @@ def _load() -> C.CDLL:
         "krk_piece_stream_placement": (i, [vp, C.POINTER(C.c_int)]),
         "krk_verify_pieces_dev": (i, [blobp, u32p, u8p, vp]),
         "krk_verify_pieces_host": (i, [C.POINTER(vp), u64p, u32p, C.c_uint64, u8p]),
+        "krk_bitfield_words": (C.c_uint64, [C.c_uint64]),
+        "krk_piece_bitfield": (i, [u32p, u32p, C.c_uint64, u64p, u32p]),
+        "krk_verify_batch_dev": (i, [blobp, C.c_uint64, u32p, u8p, vp, vp, vp, vp]),
+        "krk_verify_files": (i, [C.POINTER(krk_file_blob), C.c_uint64, u32p, u8p, u64p, u32p, u8p]),
         "krk_sha256_dev": (i, [C.POINTER(vp), u64p, C.c_uint64, vp, vp]),
         "krk_sha256_host": (i, [C.POINTER(vp), u64p, C.c_uint64, u8p]),
         "krk_sha256_dev_on_host": (i, [C.POINTER(vp), u64p, C.c_uint64, i, vp, u8p]),

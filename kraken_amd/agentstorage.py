@@ -9,9 +9,11 @@ download file at the piece's offset and the piece is marked complete.
 ``Torrent.WritePieces`` is the batched form the reference lacks: the dispatcher
 (lib/torrent/scheduler/dispatch/dispatcher.go:531-560) hands over every piece
 received since the last call, and one ``krk_verify_pieces_host`` call checks them
-all on the GPU instead of one ``hash.Hash32`` per piece.  The download-file and
-piece-status machinery around it (CADownloadStore, pieces.go metadata) is out of
-scope; a plain file stands in for it.
+all on the GPU instead of one ``hash.Hash32`` per piece.  ``Torrent.Recheck``
+re-reads the download file against the metainfo (``krk_verify_files``) and takes
+the resulting Bitfield() as the piece status.  The download-file and piece-status
+machinery around it (CADownloadStore, pieces.go metadata) is out of scope; a plain
+file stands in for it.
 """
 from __future__ import annotations
 
@@ -83,6 +85,16 @@ class Torrent:
             f.seek(self.getFileOffset(pi))
             f.write(memoryview(data))
         self.complete[pi] = True
+
+    def Recheck(self) -> np.ndarray:
+        """The recheck the reference lacks: the download file's pieces against the metainfo's
+        sums in one pass (krk_verify_files), answered as Bitfield() (torrent.go:130-140) and
+        taken over as the torrent's piece status -- what a client does after a crash, where
+        ``complete`` otherwise only knows what WritePiece saw.  Returns ``complete`` (bools)."""
+        from . import device as D
+        bits, _, _, _ = D.verify_files([self.path], [self.mi.Length()], self.mi.PieceLength(), self.mi.PieceSums())
+        self.complete = D.bitfield_bools(bits, self.NumPieces())
+        return self.complete
 
     def WritePiece(self, data, pi: int) -> None:
         """torrent.go:203-220 + writePiece :174-199 for one piece."""

@@ -163,6 +163,26 @@ static_assert(sizeof(InfoHashJob) == 64, "InfoHashJob layout");
 hipError_t launch_info_hash(const InfoHashJob* jobs, uint32_t n_jobs, const uint32_t* sums, const uint8_t* names,
                             uint8_t* out20, hipStream_t s);
 
+// ---------------------------------------------------------------- piece bitfield
+// One blob of a verify batch (piece_bitfield.hip): its sums are sums[first_sum, +n_pieces) and
+// it is checked against expected[first_sum, +n_pieces); its bitfield is the ceil(n_pieces / 64)
+// words from bits[first_word].  first_word ascends with the blob index (blob i's words follow
+// blob i-1's) and blobs[0].first_word == 0.
+struct alignas(16) BitfieldBlob {
+    uint64_t first_sum;
+    uint64_t n_pieces;  // < 2^32
+    uint64_t first_word;
+    uint64_t pad;
+};
+static_assert(sizeof(BitfieldBlob) == 32, "BitfieldBlob layout");
+// bits[w] bit l = (piece 64 (w - first_word) + l of w's blob matches), n_bad[b] = blob b's
+// mismatching pieces: every one of the n_words words and n_blobs counts is stored.
+hipError_t launch_piece_bitfield(const BitfieldBlob* blobs, uint64_t n_blobs, uint64_t n_words, const uint32_t* sums,
+                                 const uint32_t* expected, uint64_t* bits, uint32_t* n_bad, hipStream_t s);
+// ok[i] = (digests[32 i, +32) == expected[32 i, +32)); both 16-byte aligned.
+hipError_t launch_digest_equal(const uint8_t* digests, const uint8_t* expected, uint64_t n, uint8_t* ok,
+                               hipStream_t s);
+
 // ---------------------------------------------------------------- host gather
 // One tile of a host -> device gather (gather.hip): n <= kGatherTile bytes from src (a
 // device-visible address of page-locked host memory: a hipHostMalloc'd or registered

@@ -3,6 +3,7 @@ parity tests): an HBM arena of synthetic blobs and the batch calls on it."""
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -479,6 +480,139 @@ def piece_sums_files(paths, lengths, piece_lengths, multi: bool = False):
     fn = lib.krk_piece_sums_files_multi if multi else lib.krk_piece_sums_files
     check(fn(arr, n, sums.ctypes.data_as(C.POINTER(C.c_uint32))))
     return sums, offs
+
+
+def bitfield_offsets(n_pieces) -> np.ndarray:
+    """First bitfield word of each blob of a verify batch, and the total as the last entry:
+    blob i's krk_bitfield_words(n_pieces[i]) words follow blob i-1's."""
+    words = (np.asarray(n_pieces, dtype=np.uint64) + np.uint64(63)) // np.uint64(64)
+    offs = np.zeros(words.size + 1, dtype=np.uint64)
+    offs[1:] = np.cumsum(words)
+    return offs
+
+
+def bitfield_bools(words: np.ndarray, n_pieces: int) -> np.ndarray:
+    """A blob's bitfield words (willf/bitset: piece i = bit i & 63 of word i >> 6) as bools."""
+    w = np.ascontiguousarray(words, dtype="<u8")
+    return np.unpackbits(w.view(np.uint8), bitorder="little")[:int(n_pieces)].astype(bool)
+
+
+def piece_bitfield(sums, expected):
+    """krk_piece_bitfield: (bitfield words, mismatching pieces) of one blob from sums on the
+    host -- pure host code, the same bits the device kernel gives."""
+    s = np.ascontiguousarray(sums, dtype=np.uint32)
+    e = np.ascontiguousarray(expected, dtype=np.uint32)
+    if s.size != e.size:
+        raise ValueError(f"piece_bitfield: {s.size} sums against {e.size} expected")
+    bits = np.zeros(int(lib.krk_bitfield_words(s.size)), dtype=np.uint64)
+    bad = C.c_uint32()
+    u32p = C.POINTER(C.c_uint32)
+    check(lib.krk_piece_bitfield(s.ctypes.data_as(u32p) if s.size else None, e.ctypes.data_as(u32p) if s.size else None,
+                                 s.size, bits.ctypes.data_as(C.POINTER(C.c_uint64)) if bits.size else None,
+                                 C.byref(bad)))
+    return bits, bad.value
+
+
+class VerifyOutputs:
+    """The outputs of verify_batch over an arena, in device memory or (pinned=True) in
+    page-locked host memory the kernels write over PCIe: .bits (uint64, bitfield_offsets
+    layout), .n_bad (uint32 a blob), .digest_ok (uint8 a blob; only with digests)."""
+
+    def __init__(self, arena: BlobArena, digests: bool = False, pinned: bool = False):
+        n = len(arena.lengths)
+        self.word_off = bitfield_offsets(arena.n_pieces)
+        self.n, self.words, self.pinned = n, int(self.word_off[-1]), pinned
+        if pinned:
+            self.bits = PinnedArray((max(self.words, 1),), np.uint64)
+            self.n_bad = PinnedArray((max(n, 1),), np.uint32)
+            self.digest_ok = PinnedArray((max(n, 1),), np.uint8) if digests else None
+        else:
+            self.bits = DeviceBuffer(max(self.words, 1) * 8)
+            self.n_bad = DeviceBuffer(max(n, 1) * 4)
+            self.digest_ok = DeviceBuffer(max(n, 1)) if digests else None
+
+    def fill(self, byte: int):
+        """Every output byte set to `byte` (tests: the call must overwrite all of it)."""
+        for b, dt in ((self.bits, np.uint64), (self.n_bad, np.uint32), (self.digest_ok, np.uint8)):
+            if b is None:
+                continue
+            if self.pinned:
+                b.a.view(np.uint8)[:] = byte
+            else:
+                b.from_host(np.full(b.nbytes, byte, dtype=np.uint8))
+
+    def to_host(self):
+        """(bits, n_bad, digest_ok or None) as numpy arrays, once the call's stream has run."""
+        def get(b, dt, k):
+            if b is None:
+                return None
+            return b.a[:k].copy() if self.pinned else b.to_host(dt, k)
+        ok = get(self.digest_ok, np.uint8, self.n)
+        return get(self.bits, np.uint64, self.words), get(self.n_bad, np.uint32, self.n), \
+            (None if ok is None else ok.astype(bool))
+
+
+def verify_batch(arena: BlobArena, expected, digests=None, out: VerifyOutputs | None = None, stream=None):
+    """krk_verify_batch_dev: the arena's blobs against the piece sums their metainfo stores
+    (`expected`, uint32, arena layout: blob i's at arena.sums_off[i]) and, with `digests`
+    ((n, 32) uint8: the blobs' names), their SHA-256.  One wave ballots 64 pieces of a blob into
+    one willf/bitset word.  out: VerifyOutputs to fill asynchronously on `stream` (returned);
+    None: (bits, n_bad, digest_ok or None), returned once the stream has run the call."""
+    n = len(arena.lengths)
+    exp = np.ascontiguousarray(expected, dtype=np.uint32)
+    if exp.size < arena.total_pieces:
+        raise ValueError(f"verify_batch: {exp.size} expected sums for {arena.total_pieces} pieces")
+    dg = None
+    if digests is not None:
+        dg = np.ascontiguousarray(digests, dtype=np.uint8).reshape(-1)
+        if dg.size != 32 * n:
+            raise ValueError(f"verify_batch: {dg.size} digest bytes for {n} blobs")
+    dst = VerifyOutputs(arena, digests=dg is not None, pinned=True) if out is None else out
+    check(lib.krk_verify_batch_dev(arena.blob_structs(), n, exp.ctypes.data_as(C.POINTER(C.c_uint32)) if exp.size else None,
+                                   dg.ctypes.data_as(C.POINTER(C.c_uint8)) if dg is not None else None,
+                                   dst.bits.ptr, dst.n_bad.ptr, dst.digest_ok.ptr if dst.digest_ok is not None else None,
+                                   stream))
+    if out is not None:
+        return out
+    check(lib.krk_stream_sync(stream))
+    return dst.to_host()
+
+
+def verify_files(paths, lengths, piece_lengths, expected, digests=None):
+    """krk_verify_files: cache or download files against the piece sums their metainfo stores
+    (`expected`: uint32, file i's sums after file i-1's) and, with `digests` ((n, 32) uint8),
+    their SHA-256 -- krk_piece_sums_files underneath (the CRC placement rule; HOST needs no
+    device), or krk_metainfo_digest_files with digests (one read a byte feeds both).  lengths:
+    the sizes the caller stat-ed.  Returns (bits, word offsets (bitfield_offsets), n_bad,
+    digest_ok or None)."""
+    n = len(paths)
+    L = np.asarray(lengths, dtype=np.uint64)
+    pls = np.broadcast_to(np.asarray(piece_lengths, dtype=np.int64), (n,))
+    counts = [int(lib.krk_num_pieces(int(l), int(p))) if p > 0 else 0 for l, p in zip(L, pls)]
+    offs = np.zeros(n + 1, dtype=np.uint64)
+    offs[1:] = np.cumsum(counts) if n else []
+    exp = np.ascontiguousarray(expected, dtype=np.uint32)
+    if exp.size < int(offs[-1]):
+        raise ValueError(f"verify_files: {exp.size} expected sums for {int(offs[-1])} pieces")
+    dg = None
+    if digests is not None:
+        dg = np.ascontiguousarray(digests, dtype=np.uint8).reshape(-1)
+        if dg.size != 32 * n:
+            raise ValueError(f"verify_files: {dg.size} digest bytes for {n} files")
+    enc = [os.fsencode(p) for p in paths]
+    arr = (krk_file_blob * max(n, 1))()
+    for i in range(n):
+        arr[i] = krk_file_blob(enc[i], int(L[i]), int(pls[i]), int(offs[i]))
+    woff = bitfield_offsets(counts)
+    bits = np.zeros(max(int(woff[-1]), 1), dtype=np.uint64)
+    bad = np.zeros(max(n, 1), dtype=np.uint32)
+    ok = np.zeros(max(n, 1), dtype=np.uint8) if dg is not None else None
+    u8p = C.POINTER(C.c_uint8)
+    check(lib.krk_verify_files(arr, n, exp.ctypes.data_as(C.POINTER(C.c_uint32)) if exp.size else None,
+                               dg.ctypes.data_as(u8p) if dg is not None else None,
+                               bits.ctypes.data_as(C.POINTER(C.c_uint64)), bad.ctypes.data_as(C.POINTER(C.c_uint32)),
+                               ok.ctypes.data_as(u8p) if ok is not None else None))
+    return bits[:int(woff[-1])], woff, bad[:n], (ok[:n].astype(bool) if ok is not None else None)
 
 
 PLACE_AUTO, PLACE_HOST, PLACE_GPU = 0, 1, 2

@@ -7,6 +7,8 @@
   (SURVEY.md §8(f) row 2): one pass over many cache files (krk_piece_sums_files).
 * ``Generator.VerifyAndGenerateBatch`` / ``VerifyAndGenerateUploads``: upload verification
   fused with Generate, over upload bytes or the upload files.
+* ``Generator.VerifyAll``: the read-only scrub -- every cached blob against the _torrentmeta
+  stored for it (krk_verify_files: piece bitfields, and the SHA-256 against the name).
 
 The CAS store itself (lib/store) is out of scope; ``DirCAS`` is a minimal
 stand-in exposing the three calls Generate makes.
@@ -76,6 +78,12 @@ class DirCAS:
         """The cache file's path (base FileOp.GetFilePath): lets GenerateBatch read
         the file natively into pinned staging instead of through a reader."""
         return os.path.join(self._dir(hex_), "data")
+
+    def GetCacheFileMetadata(self, hex_: str) -> bytes:
+        """The _torrentmeta sidecar's bytes (base FileOp.GetFileMetadata); FileNotFoundError
+        when the blob has none."""
+        with open(os.path.join(self._dir(hex_), "_torrentmeta"), "rb") as f:
+            return f.read()
 
     def SetCacheFileMetadata(self, hex_: str, mi: core.MetaInfo) -> bool:
         p = os.path.join(self._dir(hex_), "_torrentmeta")
@@ -161,6 +169,85 @@ class Generator:
                 seen += len(batch)
                 batch, size = [], 0
         return {"blobs": seen, "changed": changed}
+
+    def VerifyAll(self, batch_bytes: int = 8 << 30, check_digest: bool = True) -> dict:
+        """The read-only counterpart of RegenerateAll: every cached blob against the
+        _torrentmeta already stored for it.  Nothing is written, renamed or deleted.
+
+        Each sidecar is loaded with DeserializeMetaInfo; found without reading data: no sidecar
+        (reason ``missing_meta``), one that does not parse or cannot describe the file
+        (``bad_meta``, with the ``error`` text), a stored Name that is not the directory's
+        (``name``), a stored Length that is not the stat size (``length``).  The rest go through
+        krk_verify_files in batches of ~batch_bytes, with the STORED piece length and sums (not
+        the config's) and, with check_digest, the blob's name as its SHA-256: reason ``pieces``
+        with the mismatching piece indices, or ``digest`` when every piece sum agrees and the
+        digest does not -- a sidecar regenerated over rotten bytes.  Returns {"blobs": n,
+        "ok": k, "corrupt": [{"name", "reason", "bad_pieces", "digest_ok"}]} sorted by name."""
+        from . import device as D
+        from ._capi import KrakenError
+        names = self.cas.ListNames()
+        corrupt, batch, size = [], [], 0
+
+        def entry(name, reason, bad_pieces=(), digest_ok=None, **more):
+            corrupt.append({"name": name, "reason": reason, "bad_pieces": [int(x) for x in bad_pieces],
+                            "digest_ok": digest_ok, **more})
+
+        def flush():
+            nonlocal batch, size
+            if not batch:
+                return
+            exp = np.concatenate([mi.PieceSums() for _, mi in batch] + [np.zeros(0, np.uint32)])
+            dg = (np.frombuffer(b"".join(bytes.fromhex(name) for name, _ in batch), dtype=np.uint8)
+                  if check_digest else None)
+            try:
+                bits, woff, bad, ok = D.verify_files([self.cas.GetCacheFilePath(name) for name, _ in batch],
+                                                     [mi.Length() for _, mi in batch],
+                                                     [mi.PieceLength() for _, mi in batch], exp, dg)
+            except KrakenError as e:
+                if e.code == KRK_EIO:
+                    raise IOError(f"verify: {e}") from None
+                raise
+            for k, (name, mi) in enumerate(batch):
+                dig_ok = bool(ok[k]) if ok is not None else None
+                if bad[k]:
+                    good = D.bitfield_bools(bits[int(woff[k]):int(woff[k + 1])], mi.NumPieces())
+                    entry(name, "pieces", np.flatnonzero(~good), dig_ok)
+                elif dig_ok is False:
+                    entry(name, "digest", (), False)
+            batch, size = [], 0
+
+        for name in names:
+            try:
+                raw = self.cas.GetCacheFileMetadata(name)
+            except FileNotFoundError:
+                entry(name, "missing_meta")
+                continue
+            try:
+                mi = core.DeserializeMetaInfo(raw)
+            except ValueError as e:
+                entry(name, "bad_meta", error=str(e))
+                continue
+            if mi.Digest().Hex() != name:
+                entry(name, "name")
+                continue
+            st_size = self.cas.GetCacheFileStat(name).st_size
+            if mi.Length() != st_size:
+                entry(name, "length")
+                continue
+            if mi.PieceLength() <= 0:
+                entry(name, "bad_meta", error="piece length must be positive")
+                continue
+            want = int(lib.krk_num_pieces(st_size, mi.PieceLength()))
+            if mi.NumPieces() != want:
+                entry(name, "bad_meta", error=f"{mi.NumPieces()} piece sums for {want} pieces")
+                continue
+            batch.append((name, mi))
+            size += st_size
+            if size >= batch_bytes:
+                flush()
+        flush()
+        corrupt.sort(key=lambda c: c["name"])
+        return {"blobs": len(names), "ok": len(names) - len(corrupt), "corrupt": corrupt}
 
     def GenerateBatch(self, digests) -> list[core.MetaInfo]:
         """Generate for many cache files in one pipelined GPU pass.  When the CAS
@@ -320,7 +407,10 @@ def _parse_config(text: str) -> dict:
 
 def main(argv=None) -> int:
     """python -m kraken_amd.metainfogen <cache dir> [--piece-lengths 0:4194304]:
-    regenerate every _torrentmeta of a CAS cache directory on the GPU."""
+    regenerate every _torrentmeta of a CAS cache directory on the GPU.  With --verify
+    [--no-digest] nothing is written: every blob is checked against its stored _torrentmeta
+    (and its name, unless --no-digest), the report is printed and the exit code is 1 when
+    anything is corrupt."""
     import argparse
     import json
     ap = argparse.ArgumentParser(description=main.__doc__)
@@ -329,10 +419,23 @@ def main(argv=None) -> int:
                     help="size:pieceLength ranges (config/origin/base.yaml:24-26 default: 0:4MB)")
     ap.add_argument("--batch-gib", type=int, default=8)
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--verify", action="store_true",
+                    help="read-only: check every blob against its stored _torrentmeta (Generator.VerifyAll)")
+    ap.add_argument("--no-digest", action="store_true", help="with --verify: piece sums only, no SHA-256 pass")
     a = ap.parse_args(argv)
     from . import device
-    device.set_device(a.device)
+    from ._capi import KRK_ENODEV, KrakenError
+    try:
+        device.set_device(a.device)
+    except KrakenError as e:
+        # the piece-sum scrub runs on the host CRC placement where there is no device
+        if not (e.code == KRK_ENODEV and a.verify and a.no_digest):
+            raise
     g = New(_parse_config(a.piece_lengths), DirCAS(a.cache_dir))
+    if a.verify:
+        report = g.VerifyAll(a.batch_gib << 30, check_digest=not a.no_digest)
+        print(json.dumps(report))
+        return 1 if report["corrupt"] else 0
     print(json.dumps(g.RegenerateAll(a.batch_gib << 30)))
     return 0
 
