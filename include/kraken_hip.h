@@ -67,7 +67,11 @@ typedef struct krk_blob {
 uint64_t krk_num_pieces(uint64_t length, int64_t piece_length);
 
 /* Device-resident batch: sums_dev (device, uint32) receives every blob's sums
- * at blobs[i].sums_offset.  Asynchronous on `stream`. */
+ * at blobs[i].sums_offset.  Asynchronous on `stream`.
+ * A call owns the span of sums_dev from its lowest sums_offset to its highest end
+ * (sums_offset + krk_num_pieces): the span is zeroed before the sums are XOR-ed in, so words
+ * in a gap between two blobs' ranges come back zero; words outside the span are not touched.
+ * Give each call its own span. */
 int krk_piece_sums_dev(const krk_blob* blobs, uint64_t n_blobs, uint32_t* sums_dev, void* stream);
 
 /* Host batch (end-to-end): blobs[i].data are HOST pointers; sums_host receives
@@ -287,7 +291,9 @@ int krk_engine_set_pool_cap(uint64_t bytes, uint64_t* cap_out, uint64_t* waits_o
  * uploader.verify (origin/blobserver/uploader.go:74-94) and the piece sums of
  * Generate (lib/metainfogen/generator.go:41-58).  The SHA and CRC kernels run
  * concurrently on two internal streams joined back into `stream`.  Device
- * pointers; asynchronous. */
+ * pointers; asynchronous.  As with krk_piece_sums_dev, a call owns the span of sums_dev from
+ * its lowest sums_offset to its highest end (gaps inside it come back zero): give each call
+ * its own span. */
 int krk_metainfo_digest_dev(const krk_blob* blobs, uint64_t n_blobs, uint32_t* sums_dev,
                             uint8_t* digests_dev, void* stream);
 

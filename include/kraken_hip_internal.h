@@ -181,6 +181,11 @@ int krk_synth_fill_chunks_dev(const krk_chunk* chunks, uint64_t n, int variant, 
 int krk_device_pci_bus_id(char* out, uint32_t cap);
 /* CUs of the calling thread's device. */
 int krk_device_cus(int* out);
+/* The CRC launch variant (crc32_pieces.hip launch_crc_items) every piece-CRC launch of the
+ * calling thread's device uses: 16 in the production library; the diagnostic build reads
+ * KRK_CRC_VARIANT once per device context, and a value it does not know falls back to 16.
+ * Read-only -- there is no setter: a test asks which kernel it actually ran. */
+int krk_crc_launch_variant(int* out);
 
 /* ---------------------------------------------------------- kernel timing
  * When enabled, every kernel launch is bracketed by hipEvents recorded on the stream

@@ -100,7 +100,7 @@ struct CrcWork {
 
 struct CrcLaunchCfg {
     int cus;           // compute units
-    int variant;       // crc32_pieces.hip launch_crc_items; default 7 (byte-addressable tables)
+    int variant;       // crc32_pieces.hip launch_crc_items; default 16 (byte-addressable tables, work queue)
 };
 
 bool crc_variant_valid(int variant);

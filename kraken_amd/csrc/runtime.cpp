@@ -364,6 +364,12 @@ int krk_device_cus(int* out) {
     *out = D->cus;
     return KRK_OK;
 }
+int krk_crc_launch_variant(int* out) {
+    KRK_CHECK(out, KRK_EINVAL, "out is NULL");
+    KRK_DEVICE(D);
+    *out = D->crc_variant;
+    return KRK_OK;
+}
 int krk_stream_create_prio(int priority, void** out) {
     KRK_CHECK(out, KRK_EINVAL, "out is NULL");
     KRK_DEVICE(D);

@@ -100,6 +100,11 @@ def test_sums_offsets_are_respected(gpu, orc):
     r1 = orc.calc_piece_sums(orc.synth(4, 9000), 1000)[1]
     assert np.array_equal(got[20:25], r0)
     assert np.array_equal(got[2:11], r1)
+    # a call owns the span from its lowest sums offset to its highest end (kraken_hip.h): the
+    # gap inside it comes back zero, the words outside it are not touched
+    lo, hi = 2, 25
+    assert np.all(got[11:20] == 0)
+    assert np.all(got[:lo] == 0xDEADBEEF) and np.all(got[hi:] == 0xDEADBEEF)
 
 
 def test_verify_pieces(gpu, orc):
