@@ -446,8 +446,10 @@ typedef struct krk_nodes {
 
 /* keys: concatenated hex strings with key_off (n_keys+1).  order_out:
  * n_keys * n_out node indices (-1 padded when n_out > n_nodes); scores_out
- * (nullable): n_keys * n_nodes, in node order.  Returns KRK_EHEX if any key is
- * not valid hex (its row is then filled from NaN scores: node order). */
+ * (nullable): n_keys * n_nodes, in node order -- also with n_out == 0, which asks for
+ * scores alone.  Returns KRK_EHEX if any key is not valid hex (its row is then filled
+ * from NaN scores: node order).  n_nodes of 0 or above 4096 and n_out above 4096 are
+ * KRK_EINVAL, refused before anything is launched or written. */
 int krk_hrw_ordered(const char* keys, const uint64_t* key_off, uint64_t n_keys,
                     const krk_nodes* nodes, uint32_t n_out, int32_t* order_out,
                     double* scores_out);
@@ -460,7 +462,9 @@ int krk_hrw_uint64_to_float64(const uint8_t* sums8, uint64_t n, int rehash, doub
 
 /* ring.Locations for raw 32-byte sha256 digests (ShardID = first 2 bytes).
  * healthy: n_nodes flags.  locs_out: n * max(1, max_replica) node indices
- * (-1 padded); counts_out: n entries. */
+ * (-1 padded); counts_out: n entries.  Counts are one byte: a ring whose shards can have
+ * more than 255 owners, min(max_replica, n_nodes) > 255, is KRK_ERANGE, refused before
+ * anything is launched or written (300 nodes with max_replica 255 are served). */
 int krk_ring_locations(const uint8_t* digests32, uint64_t n, const krk_nodes* nodes,
                        const uint8_t* healthy, int32_t max_replica,
                        int32_t* locs_out, uint8_t* counts_out);
@@ -469,7 +473,8 @@ int krk_ring_locations(const uint8_t* digests32, uint64_t n, const krk_nodes* no
  * once per membership or health change (ring.Refresh, lib/hashring/ring.go:141-165)
  * and Locations becomes a host lookup: row ((d[0] << 8) | d[1]) of locs_out
  * (65,536 x max(1, max_replica) node indices, -1 padded) with counts_out[row] valid
- * entries.  Same semantics as krk_ring_locations. */
+ * entries.  Same semantics as krk_ring_locations, KRK_ERANGE for
+ * min(max_replica, n_nodes) > 255 included. */
 int krk_ring_owner_table(const krk_nodes* nodes, const uint8_t* healthy, int32_t max_replica,
                          int32_t* locs_out, uint8_t* counts_out);
 /* Device-resident form (digests in device memory).  The owner table of a membership
@@ -478,13 +483,15 @@ int krk_ring_owner_table(const krk_nodes* nodes, const uint8_t* healthy, int32_t
  * hrw until Refresh; later calls only gather.  locs/counts: device memory, or page-locked
  * host memory (krk_host_alloc) that the gather writes over PCIe -- the owner lists are on
  * the host when the stream reaches the call's end, with no copy-back; any other pointer is
- * KRK_EINVAL. */
+ * KRK_EINVAL.  min(max_replica, n_nodes) > 255 is KRK_ERANGE (8-bit counts, as
+ * krk_ring_locations), refused before any table is built or output written. */
 int krk_ring_locations_dev(const uint8_t* digests32_dev, uint64_t n, const krk_nodes* nodes,
                            const uint8_t* healthy, int32_t max_replica,
                            int32_t* locs_dev, uint8_t* counts_dev, void* stream);
 /* Compact form for rings of <= 255 nodes (KRK_ERANGE beyond): owner indices as
  * uint8 (0xFF padded), a quarter of the bytes the caller copies back.  Same
- * ring.Locations semantics (lib/hashring/ring.go:91-118) as krk_ring_locations_dev. */
+ * ring.Locations semantics (lib/hashring/ring.go:91-118) as krk_ring_locations_dev, its
+ * KRK_ERANGE for min(max_replica, n_nodes) > 255 included. */
 int krk_ring_locations_u8_dev(const uint8_t* digests32_dev, uint64_t n, const krk_nodes* nodes,
                               const uint8_t* healthy, int32_t max_replica,
                               uint8_t* locs_dev, uint8_t* counts_dev, void* stream);

@@ -140,7 +140,8 @@ int krk_hrw_ordered(const char* keys, const uint64_t* key_off, uint64_t n_keys, 
     if (!r) {
         HrwArgs a{static_cast<const uint8_t*>(d_kb), static_cast<const uint64_t*>(d_koff), n_keys, dn.labels, dn.off,
                   dn.w, N, n_out, static_cast<const uint8_t*>(d_bad), d_order, d_sc};
-        hipError_t e = n_out ? timed(K_HRW, s, [&] { return launch_hrw_order(a, s); }) : hipSuccess;
+        // n_out == 0 with scores wanted still scores (the kernel then writes no order entry)
+        hipError_t e = n_out || d_sc ? timed(K_HRW, s, [&] { return launch_hrw_order(a, s); }) : hipSuccess;
         if (e != hipSuccess) { set_error(KRK_EHIP, "hrw launch: %s", launch_error_text(e)); r = KRK_EHIP; }
     }
     // Copy-out: drain the stream, then blocking copies into the caller's (pageable) memory.
@@ -197,10 +198,21 @@ static void shard_keys(std::vector<uint8_t>& kb, std::vector<uint64_t>& koff, co
     koff[shards.size()] = kb.size();
 }
 
+// Owner counts are one byte each (counts_out, the table's d_tc, the packed rows): a shard of
+// a ring of more than 255 nodes with MaxReplica past 255 would have more owners than a count
+// can say.  Refused before anything is launched or written.
+static int check_owner_count(const krk_nodes* nodes, int32_t max_replica) {
+    const int64_t most = std::min<int64_t>(max_replica, nodes->n_nodes);
+    KRK_CHECK(most <= 255, KRK_ERANGE, "ring: up to %lld owners a shard do not fit the 8-bit owner counts (<= 255)",
+              (long long)most);
+    return KRK_OK;
+}
+
 int krk_ring_locations(const uint8_t* digests32, uint64_t n, const krk_nodes* nodes, const uint8_t* healthy,
                        int32_t max_replica, int32_t* locs_out, uint8_t* counts_out) {
     if (!n) return KRK_OK;
-    KRK_CHECK(digests32 && healthy && locs_out && counts_out, KRK_EINVAL, "ring_locations: null argument");
+    KRK_CHECK(digests32 && nodes && healthy && locs_out && counts_out, KRK_EINVAL, "ring_locations: null argument");
+    if (const int rc = check_owner_count(nodes, max_replica)) return rc;
     KRK_DEVICE(D);
     hipStream_t s = D->s_main;
     const uint32_t row_out = (uint32_t)std::max<int32_t>(1, max_replica);
@@ -430,6 +442,7 @@ static int ring_locations_dev(const uint8_t* digests32_dev, uint64_t n, const kr
               "ring_locations_dev: null argument");
     KRK_CHECK(sizeof(T) != 1 || nodes->n_nodes <= 255, KRK_ERANGE,
               "ring_locations_u8_dev: %u nodes do not fit 8-bit owner indices (<= 255)", nodes->n_nodes);
+    if (const int rc = check_owner_count(nodes, max_replica)) return rc;
     KRK_DEVICE(D);
     hipStream_t s = pick(D, stream);
     const uint32_t row_out = (uint32_t)std::max<int32_t>(1, max_replica);
@@ -462,6 +475,7 @@ extern "C" {
 int krk_ring_owner_table(const krk_nodes* nodes, const uint8_t* healthy, int32_t max_replica, int32_t* locs_out,
                          uint8_t* counts_out) {
     KRK_CHECK(nodes && healthy && locs_out && counts_out, KRK_EINVAL, "ring_owner_table: null argument");
+    if (const int rc = check_owner_count(nodes, max_replica)) return rc;
     KRK_DEVICE(D);
     hipStream_t s = D->s_main;
     const uint32_t row_out = (uint32_t)std::max<int32_t>(1, max_replica);
