@@ -186,6 +186,19 @@ int krk_device_cus(int* out);
  * KRK_CRC_VARIANT once per device context, and a value it does not know falls back to 16.
  * Read-only -- there is no setter: a test asks which kernel it actually ran. */
 int krk_crc_launch_variant(int* out);
+/* The windows' gather launch (gather.hip) on spans the caller lays out: span i copies n[i] bytes
+ * of page-locked host memory at src[i] (any alignment) to dst[i], all `count` spans in one
+ * launch queued on `stream` (NULL = the library's stream); asynchronous.  The kernel stores
+ * whole 16-byte words, so dst[i] must be 16-byte aligned and writable by the device over n[i]
+ * rounded up to 16 -- the bytes past n[i] of that room are unspecified afterwards -- and src[i]
+ * must be page-locked memory the device maps at its host address, the check the windows make
+ * before they gather (a krk_host_alloc block, or memory registered with the HIP runtime).
+ * Anything else is KRK_EINVAL before any launch: a pageable source is refused, never read.
+ * A span of n[i] == 0 copies nothing (its src may be NULL); count == 0 is KRK_OK.  For the
+ * tests, which compare the gathered bytes and their surroundings with the source; the
+ * product reaches the gather through the window loop only. */
+int krk_gather_spans_dev(const void* const* src, void* const* dst, const uint64_t* n, uint64_t count,
+                         void* stream);
 
 /* ---------------------------------------------------------- kernel timing
  * When enabled, every kernel launch is bracketed by hipEvents recorded on the stream

@@ -178,6 +178,7 @@ def _load() -> C.CDLL:
         "krk_stream_create_prio": (i, [i, C.POINTER(vp)]),
         "krk_device_cus": (i, [C.POINTER(i)]),
         "krk_crc_launch_variant": (i, [C.POINTER(i)]),
+        "krk_gather_spans_dev": (i, [C.POINTER(vp), C.POINTER(vp), u64p, C.c_uint64, vp]),
         "krk_device_pci_bus_id": (i, [C.c_char_p, C.c_uint32]),
         "krk_stream_destroy": (i, [vp]),
         "krk_stream_sync": (i, [vp]),

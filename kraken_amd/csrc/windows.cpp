@@ -929,6 +929,30 @@ int krk_set_host_gather(int mode) {
     return KRK_OK;
 }
 
+// The windows' gather launch on spans the caller lays out (tests): every span is checked as
+// the windows check theirs before anything is queued.
+int krk_gather_spans_dev(const void* const* src, void* const* dst, const uint64_t* n, uint64_t count, void* stream) {
+    if (!count) return KRK_OK;
+    KRK_CHECK(src && dst && n, KRK_EINVAL, "gather_spans_dev: null argument");
+    KRK_DEVICE(D);
+    MappedAtHost at_host;
+    std::vector<GatherSpan> spans;
+    spans.reserve(count);
+    for (uint64_t i = 0; i < count; ++i) {
+        KRK_CHECK(!(reinterpret_cast<uintptr_t>(dst[i]) & 15), KRK_EINVAL,
+                  "gather_spans_dev: dst of span %llu is not 16-byte aligned", (unsigned long long)i);
+        if (!n[i]) continue;
+        KRK_CHECK(n[i] < (1ull << 60) && dst[i] && device_writable(dst[i], (n[i] + 15) & ~15ull), KRK_EINVAL,
+                  "gather_spans_dev: dst of span %llu must be device-writable over its length rounded up to 16",
+                  (unsigned long long)i);
+        KRK_CHECK(src[i] && at_host(src[i], n[i]), KRK_EINVAL,
+                  "gather_spans_dev: src of span %llu is not page-locked memory mapped at its host address",
+                  (unsigned long long)i);
+        spans.push_back({static_cast<uint8_t*>(dst[i]), static_cast<const uint8_t*>(src[i]), n[i]});
+    }
+    return run_gather(D, spans, pick(D, stream));
+}
+
 int krk_windows_last_gather(int* gather_windows, uint64_t* registered_bytes, double* register_seconds) {
     if (gather_windows) *gather_windows = t_last_call.gather_windows;
     if (registered_bytes) *registered_bytes = t_last_call.registered_bytes;
