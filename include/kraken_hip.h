@@ -209,6 +209,44 @@ int krk_verify_files(const krk_file_blob* files, uint64_t n_files, const uint32_
                      const uint8_t* expected_digests, uint64_t* bits_host, uint32_t* n_bad_host,
                      uint8_t* digest_ok_host);
 
+/* ------------------------------------------- re-piece stored MetaInfo, no blob read
+ * The piece sums of a stored MetaInfo at a COARSER piece length, from the stored sums alone:
+ * what a changed piece-length table (lib/metainfogen/config.go:48-80) asks of every
+ * _torrentmeta in the cache, and overwriteMetaInfo(d, pieceLength)
+ * (origin/blobserver/server.go:344-360) of one.  new_piece_length must be a multiple of
+ * piece_length (splitting pieces needs the bytes and stays with Generate).  On finalised IEEE
+ * sums crc(A || B) = shift(crc(A), |B|) ^ crc(B), shift(c, n) = c * x^(8n) mod P, so a new
+ * piece's sum is the XOR over the old pieces it covers of their sums shifted to its end: bit-exact,
+ * O(pieces), zero blob bytes.  The shift is a bijection, so a stored sum that was wrong stays
+ * wrong in the coarse sum: re-piecing neither hides nor repairs rot (krk_verify_files is the
+ * check).
+ *
+ * A blob reads krk_num_pieces(length, piece_length) sums at sums_offset and writes
+ * krk_num_pieces(length, new_piece_length) sums at out_offset; length == 0 reads and writes
+ * nothing; equal piece lengths copy; new_piece_length >= length > 0 gives one sum, the blob's
+ * whole CRC-32.  Every output sum is stored by the call; the caller pre-zeroes nothing and words
+ * between two blobs' ranges are not touched.  Refused before anything is written or launched:
+ * KRK_EINVAL "piece length must be positive", "new piece length %lld is not a multiple of piece
+ * length %lld", a negative length; krk_repiece_sums also KRK_EINVAL "%llu piece sums for %llu
+ * pieces" and KRK_ERANGE when n_out is too small. */
+typedef struct krk_repiece_blob {
+    int64_t length, piece_length, new_piece_length;
+    uint64_t sums_offset, out_offset;      /* into sums / out, in sums */
+} krk_repiece_blob;
+/* One blob; pure host code, no device. */
+int krk_repiece_sums(const uint32_t* sums, uint64_t n_sums, int64_t length, int64_t piece_length,
+                     int64_t new_piece_length, uint32_t* out, uint64_t n_out);
+/* A batch on the host; no device. */
+int krk_repiece_batch(const krk_repiece_blob* blobs, uint64_t n, const uint32_t* sums, uint32_t* out);
+/* The same on the device (piece_repiece.hip, bit-identical to the host forms): sums_dev and
+ * out_dev are device memory or page-locked host memory (krk_host_alloc); any other pointer is
+ * KRK_EINVAL before anything is launched.  Asynchronous on `stream`: the descriptors are copied
+ * into the library's staging before the call returns, so out_dev can feed
+ * krk_info_hash_batch_dev on the same stream with no host step between.  n == 0 is KRK_OK;
+ * KRK_ENODEV without a gfx950 device. */
+int krk_repiece_batch_dev(const krk_repiece_blob* blobs_host, uint64_t n, const uint32_t* sums_dev,
+                          uint32_t* out_dev, void* stream);
+
 /* ----------------------------------------------------- SHA-256 (Digester)
  * Replaces core.Digester (core/digester.go:28-72): crypto.SHA256 over the whole
  * blob.  One Merkle-Damgard stream per lane, many blobs per launch. */

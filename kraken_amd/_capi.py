@@ -36,6 +36,11 @@ class krk_file_blob(C.Structure):
                 ("sums_offset", C.c_uint64)]
 
 
+class krk_repiece_blob(C.Structure):
+    _fields_ = [("length", C.c_int64), ("piece_length", C.c_int64), ("new_piece_length", C.c_int64),
+                ("sums_offset", C.c_uint64), ("out_offset", C.c_uint64)]
+
+
 class krk_chunk(C.Structure):
     _fields_ = [("data", C.c_void_p), ("offset", C.c_uint64), ("length", C.c_uint64),
                 ("blob_length", C.c_uint64), ("piece_length", C.c_int64), ("sums_offset", C.c_uint64),
@@ -99,6 +104,9 @@ def _load() -> C.CDLL:
         "krk_piece_bitfield": (i, [u32p, u32p, C.c_uint64, u64p, u32p]),
         "krk_verify_batch_dev": (i, [blobp, C.c_uint64, u32p, u8p, vp, vp, vp, vp]),
         "krk_verify_files": (i, [C.POINTER(krk_file_blob), C.c_uint64, u32p, u8p, u64p, u32p, u8p]),
+        "krk_repiece_sums": (i, [u32p, C.c_uint64, C.c_int64, C.c_int64, C.c_int64, u32p, C.c_uint64]),
+        "krk_repiece_batch": (i, [C.POINTER(krk_repiece_blob), C.c_uint64, u32p, u32p]),
+        "krk_repiece_batch_dev": (i, [C.POINTER(krk_repiece_blob), C.c_uint64, vp, vp, vp]),
         "krk_sha256_dev": (i, [C.POINTER(vp), u64p, C.c_uint64, vp, vp]),
         "krk_sha256_host": (i, [C.POINTER(vp), u64p, C.c_uint64, u8p]),
         "krk_sha256_dev_on_host": (i, [C.POINTER(vp), u64p, C.c_uint64, i, vp, u8p]),

@@ -21,7 +21,7 @@ import json
 
 import numpy as np
 
-from ._capi import KrakenError, check, krk_blob, lib
+from ._capi import KRK_EINVAL, KrakenError, check, krk_blob, lib
 
 SHA256 = "sha256"
 DigestEmptyTar = "sha256:e3b0c44298fc1c149afbf4c8996fb92427ae41e4649b934ca495991b7852b855"
@@ -302,6 +302,26 @@ class MetaInfo:
 
     def PieceSums(self) -> np.ndarray:
         return np.zeros(0, dtype=np.uint32) if self._sums is None else self._sums
+
+    def Repiece(self, new_piece_length: int) -> "MetaInfo":
+        """This MetaInfo at a coarser piece length (a multiple of PieceLength()), from the stored
+        sums alone (krk_repiece_sums: no blob byte is read); equal, field for field and in
+        Serialize(), to NewMetaInfo(d, blob, new_piece_length) when the stored sums are the
+        blob's.  ValueError with the library's text when the length is no multiple."""
+        old = np.ascontiguousarray(self.PieceSums(), dtype=np.uint32)
+        n = int(lib.krk_num_pieces(max(self._len, 0), new_piece_length))
+        out = np.zeros(max(n, 1), dtype=np.uint32)
+        u32p = C.POINTER(C.c_uint32)
+        try:
+            check(lib.krk_repiece_sums(old.ctypes.data_as(u32p) if old.size else None, old.size, self._len, self._pl,
+                                       int(new_piece_length), out.ctypes.data_as(u32p), n))
+        except KrakenError as e:
+            if e.code == KRK_EINVAL:
+                raise ValueError(str(e)) from None
+            raise
+        sums = out[:n] if n else None
+        ih = _info_hash(int(new_piece_length), out[:n], self._name, self._len)
+        return MetaInfo(int(new_piece_length), sums, self._name, self._len, self._digest, ih)
 
     def Serialize(self) -> bytes:
         """core/metainfo.go:131-134: json of {"Info": info} (field order as declared)."""

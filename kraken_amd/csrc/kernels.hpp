@@ -183,6 +183,24 @@ hipError_t launch_piece_bitfield(const BitfieldBlob* blobs, uint64_t n_blobs, ui
 hipError_t launch_digest_equal(const uint8_t* digests, const uint8_t* expected, uint64_t n, uint8_t* ok,
                                hipStream_t s);
 
+// ---------------------------------------------------------------- re-piece
+// One blob of a re-piece batch (piece_repiece.hip): its stored sums are sums[first_old,
+// + ceil(length / po)), its new sums, for pieces of po k bytes, out[first_new, + ceil(length /
+// (po k))).  first_unit ascends with the blob index (blob i's units follow blob i-1's,
+// rp::units of repiece_math.hpp) and blobs[0].first_unit == 0.
+struct alignas(16) RepieceBlob {
+    uint64_t first_old;
+    uint64_t first_new;
+    uint64_t length;
+    uint64_t po;  // the stored piece length
+    uint64_t k;   // new piece length / po, >= 1
+    uint64_t first_unit;
+};
+static_assert(sizeof(RepieceBlob) == 48, "RepieceBlob layout");
+// Every new sum of the n_units units is stored; x8pow is the x^(8 * 2^b) table (kTabX8Pow).
+hipError_t launch_piece_repiece(const RepieceBlob* blobs, uint64_t n_blobs, uint64_t n_units, const uint32_t* x8pow,
+                                const uint32_t* sums, uint32_t* out, hipStream_t s);
+
 // ---------------------------------------------------------------- host gather
 // One tile of a host -> device gather (gather.hip): n <= kGatherTile bytes from src (a
 // device-visible address of page-locked host memory: a hipHostMalloc'd or registered

@@ -9,6 +9,10 @@
   fused with Generate, over upload bytes or the upload files.
 * ``Generator.VerifyAll``: the read-only scrub -- every cached blob against the _torrentmeta
   stored for it (krk_verify_files: piece bitfields, and the SHA-256 against the name).
+* ``Generator.OverwriteMetaInfo`` / ``RepieceAll``: a stored _torrentmeta brought to a coarser
+  piece length from its stored sums alone (krk_repiece_sums / krk_repiece_batch[_dev]) --
+  Server.overwriteMetaInfo (origin/blobserver/server.go:347-360) and a piece-length table change
+  without rereading the cache.
 
 The CAS store itself (lib/store) is out of scope; ``DirCAS`` is a minimal
 stand-in exposing the three calls Generate makes.
@@ -21,7 +25,7 @@ import os
 import numpy as np
 
 from . import core
-from ._capi import KRK_EIO, check, krk_blob, krk_file_blob, lib
+from ._capi import KRK_EIO, check, krk_blob, krk_file_blob, krk_repiece_blob, lib
 
 
 class pieceLengthConfig:
@@ -169,6 +173,136 @@ class Generator:
                 seen += len(batch)
                 batch, size = [], 0
         return {"blobs": seen, "changed": changed}
+
+    def _stored_metainfo(self, name: str, st_size: int):
+        """The blob's stored MetaInfo if it passes VerifyAll's no-read checks -- it parses, its
+        Name is the directory's, its Length the stat size, its piece length positive and its sum
+        count right -- else None."""
+        try:
+            mi = core.DeserializeMetaInfo(self.cas.GetCacheFileMetadata(name))
+        except (OSError, ValueError):
+            return None
+        if mi.Digest().Hex() != name or mi.Length() != st_size or mi.PieceLength() <= 0:
+            return None
+        if mi.NumPieces() != int(lib.krk_num_pieces(st_size, mi.PieceLength())):
+            return None
+        return mi
+
+    def OverwriteMetaInfo(self, d: core.Digest, piece_length: int) -> None:
+        """Server.overwriteMetaInfo (origin/blobserver/server.go:347-360): d's metainfo at
+        piece_length written over any existing one.  With a usable stored sidecar
+        (_stored_metainfo) whose piece length divides piece_length the new sums come from the
+        stored ones (MetaInfo.Repiece) and the blob is not read; otherwise the blob is read, as
+        the reference does.  The reference's error prefixes."""
+        mi = None
+        if piece_length > 0:
+            try:
+                stored = self._stored_metainfo(d.Hex(), self.cas.GetCacheFileStat(d.Hex()).st_size)
+            except OSError:
+                stored = None  # the reader below reports it
+            if stored is not None and piece_length % stored.PieceLength() == 0:
+                mi = stored.Repiece(piece_length)
+        if mi is None:
+            try:
+                f = self.cas.GetCacheFileReader(d.Hex())
+            except OSError as e:
+                raise IOError(f"get cache file: {e}") from None
+            with f:
+                try:
+                    mi = core.NewMetaInfo(d, f, piece_length)
+                except (ValueError, IOError) as e:
+                    raise IOError(f"create metainfo: {e}") from None
+        try:
+            self.cas.SetCacheFileMetadata(d.Hex(), mi)
+        except OSError as e:
+            raise IOError(f"set metainfo: {e}") from None
+
+    def RepieceAll(self, placement: str = "host", batch_bytes: int = 8 << 30) -> dict:
+        """Every cached blob's _torrentmeta brought to the piece length the config gives its
+        size -- what RegenerateAll writes after a piece-length table change, byte for byte --
+        reading only the blobs whose stored sums cannot serve.  Per blob, with its usable stored
+        sidecar (_stored_metainfo): the target equals the stored piece length: ``unchanged``; the
+        stored one divides it: ``repieced`` from the stored sums -- all of them in ONE
+        krk_repiece_batch call (placement "host"), or (placement "gpu") ONE krk_repiece_batch_dev
+        then krk_info_hash_batch_dev on the same stream and one copy back; everything else, a
+        missing or unusable sidecar included: ``reread`` through GenerateBatch in batches of
+        ~batch_bytes.  Returns {"blobs", "unchanged", "repieced", "reread", "changed" (sidecars
+        whose bytes changed), "bytes_not_read" (the sizes of the unchanged and repieced blobs)}."""
+        if placement not in ("host", "gpu"):
+            raise ValueError(f"unknown placement {placement!r}")
+        names = self.cas.ListNames()
+        unchanged = changed = bytes_not_read = 0
+        todo, reread = [], []
+        for name in names:
+            size = self.cas.GetCacheFileStat(name).st_size
+            target = self.pieceLengthConfig.get(size)
+            mi = self._stored_metainfo(name, size)
+            if mi is not None and target == mi.PieceLength():
+                unchanged += 1
+                bytes_not_read += size
+            elif mi is not None and target > 0 and target % mi.PieceLength() == 0:
+                todo.append((name, mi, target))
+                bytes_not_read += size
+            else:
+                reread.append((name, size))
+        if todo:
+            for (name, mi, target), (sums, ih) in zip(todo, self._repiece_batch(todo, placement)):
+                new = core.MetaInfo(target, sums, name, mi.Length(), mi.Digest(), ih)
+                try:
+                    changed += bool(self.cas.SetCacheFileMetadata(name, new))
+                except OSError as e:
+                    raise IOError(f"set metainfo: {e}") from None
+        batch, size = [], 0
+        for i, (name, n) in enumerate(reread):
+            batch.append(core.NewSHA256DigestFromHex(name))
+            size += n
+            if size >= batch_bytes or i == len(reread) - 1:
+                self.GenerateBatch(batch)
+                changed += self._last_changed
+                batch, size = [], 0
+        return {"blobs": len(names), "unchanged": unchanged, "repieced": len(todo), "reread": len(reread),
+                "changed": changed, "bytes_not_read": bytes_not_read}
+
+    def _repiece_batch(self, todo, placement: str):
+        """[(new sums or None, InfoHash)] of todo's [(name, stored MetaInfo, new piece length)]."""
+        n = len(todo)
+        arr = (krk_repiece_blob * n)()
+        a = b = 0
+        for i, (_, mi, target) in enumerate(todo):
+            arr[i] = krk_repiece_blob(mi.Length(), mi.PieceLength(), target, a, b)
+            a += mi.NumPieces()
+            b += int(lib.krk_num_pieces(mi.Length(), target))
+        old = np.concatenate([mi.PieceSums() for _, mi, _ in todo] + [np.zeros(0, np.uint32)]).astype(np.uint32)
+        offs = [int(x.out_offset) for x in arr]
+        counts = [int(lib.krk_num_pieces(mi.Length(), target)) for _, mi, target in todo]
+        pls, lens, hexes = [t for *_, t in todo], [mi.Length() for _, mi, _ in todo], [name for name, *_ in todo]
+        u32p = C.POINTER(C.c_uint32)
+        if placement == "host":
+            out = np.zeros(max(b, 1), dtype=np.uint32)
+            check(lib.krk_repiece_batch(arr, n, old.ctypes.data_as(u32p) if old.size else None, out.ctypes.data_as(u32p)))
+            ihs = core._info_hash_batch(pls, out, offs, counts, hexes, lens)
+        else:
+            from . import device as D
+            d_old = D.DeviceBuffer(4 * max(a, 1))
+            d_old.from_host(old)
+            ih_at = (4 * b + 15) & ~15  # [new sums][InfoHashes]: one buffer, one copy back
+            d_out = D.DeviceBuffer(ih_at + 20 * n)
+            back = D.PinnedArray((ih_at + 20 * n,), np.uint8)
+            check(lib.krk_repiece_batch_dev(arr, n, d_old.ptr, d_out.ptr, None))
+            buf, noff = D.pack_names(hexes)
+            i64p, u64p = C.POINTER(C.c_int64), C.POINTER(C.c_uint64)
+            col = lambda v, dt: np.ascontiguousarray(v, dtype=dt)
+            pl_, so_, ns_, ln_ = col(pls, np.int64), col(offs, np.uint64), col(counts, np.uint64), col(lens, np.int64)
+            check(lib.krk_info_hash_batch_dev(pl_.ctypes.data_as(i64p), d_out.ptr, so_.ctypes.data_as(u64p),
+                                              ns_.ctypes.data_as(u64p), buf or None, noff.ctypes.data_as(u64p),
+                                              ln_.ctypes.data_as(i64p), n, d_out.ptr + ih_at, None))
+            back.fill_from_async(d_out, None)
+            check(lib.krk_stream_sync(None))
+            out = back.a[:4 * b].view(np.uint32).copy()
+            ihs = [core.InfoHash(bytes(back.a[ih_at + 20 * i:ih_at + 20 * i + 20])) for i in range(n)]
+            d_old.free()
+            d_out.free()
+        return [(out[o:o + c].copy() if c else None, ih) for o, c, ih in zip(offs, counts, ihs)]
 
     def VerifyAll(self, batch_bytes: int = 8 << 30, check_digest: bool = True) -> dict:
         """The read-only counterpart of RegenerateAll: every cached blob against the
@@ -410,7 +544,9 @@ def main(argv=None) -> int:
     regenerate every _torrentmeta of a CAS cache directory on the GPU.  With --verify
     [--no-digest] nothing is written: every blob is checked against its stored _torrentmeta
     (and its name, unless --no-digest), the report is printed and the exit code is 1 when
-    anything is corrupt."""
+    anything is corrupt.  With --repiece [--repiece-placement gpu] the sidecars are brought to
+    --piece-lengths from their stored sums wherever the stored piece length divides the new one
+    (no blob byte read), the other blobs are reread, and the report is printed."""
     import argparse
     import json
     ap = argparse.ArgumentParser(description=main.__doc__)
@@ -422,16 +558,26 @@ def main(argv=None) -> int:
     ap.add_argument("--verify", action="store_true",
                     help="read-only: check every blob against its stored _torrentmeta (Generator.VerifyAll)")
     ap.add_argument("--no-digest", action="store_true", help="with --verify: piece sums only, no SHA-256 pass")
+    ap.add_argument("--repiece", action="store_true",
+                    help="bring every _torrentmeta to --piece-lengths from the stored sums where the stored piece "
+                         "length divides the new one, reading only the other blobs (Generator.RepieceAll)")
+    ap.add_argument("--repiece-placement", choices=("host", "gpu"), default="host",
+                    help="with --repiece: where the stored sums are re-pieced")
     a = ap.parse_args(argv)
     from . import device
     from ._capi import KRK_ENODEV, KrakenError
     try:
         device.set_device(a.device)
     except KrakenError as e:
-        # the piece-sum scrub runs on the host CRC placement where there is no device
-        if not (e.code == KRK_ENODEV and a.verify and a.no_digest):
+        # the piece-sum scrub and the host re-piece run on the host CRC placement where there is
+        # no device
+        if not (e.code == KRK_ENODEV and ((a.verify and a.no_digest) or
+                                          (a.repiece and a.repiece_placement == "host"))):
             raise
     g = New(_parse_config(a.piece_lengths), DirCAS(a.cache_dir))
+    if a.repiece:
+        print(json.dumps(g.RepieceAll(a.repiece_placement, a.batch_gib << 30)))
+        return 0
     if a.verify:
         report = g.VerifyAll(a.batch_gib << 30, check_digest=not a.no_digest)
         print(json.dumps(report))
