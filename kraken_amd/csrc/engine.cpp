@@ -48,6 +48,7 @@
 #include <unordered_map>
 #include <unordered_set>
 
+#include "engine_math.hpp"
 #include "runtime.hpp"
 
 namespace krk {
@@ -470,39 +471,9 @@ void complete_sha(Engine* E, Inflight* f) {
     E->sha_jobs.fetch_add(f->batch.size(), std::memory_order_relaxed);
 }
 
-// Portions of stream bytes [a, a+len) cut at multiples of P (P == 0: one portion).
-struct Portions {
-    uint64_t first_end;  // end of the first portion
-    uint64_t f0, f1;     // whole pieces [f0, f1) strictly inside
-    bool head, tail;     // a partial portion before / after the whole pieces
-    uint64_t count;
-};
-
-Portions portions(uint64_t a, uint64_t len, uint64_t P) {
-    Portions p{};
-    const uint64_t b = a + len;
-    if (!len) return p;
-    if (P == 0) {
-        p.head = true;
-        p.first_end = b;
-        p.count = 1;
-        return p;
-    }
-    p.f0 = (a + P - 1) / P;
-    p.f1 = b / P;
-    if (p.f1 < p.f0) {  // inside one piece, touching neither boundary
-        p.head = true;
-        p.first_end = b;
-        p.f0 = p.f1 = 0;
-        p.count = 1;
-        return p;
-    }
-    p.head = a < p.f0 * P;
-    p.tail = b > p.f1 * P;
-    p.first_end = p.head ? p.f0 * P : a;
-    p.count = (p.head ? 1 : 0) + (p.f1 - p.f0) + (p.tail ? 1 : 0);
-    return p;
-}
+// Portions of stream bytes [a, a+len) cut at multiples of P: engine_math.hpp.
+using em::Portions;
+using em::portions;
 
 int launch_crc(Engine* E, Inflight* f) {
     Device* D = E->D;
@@ -1399,22 +1370,10 @@ void stream_fold(Req* r) {
         s->fold_stop = true;
         return;
     }
-    const uint64_t a = r->off, b = r->off + r->len, P = r->P;
-    uint64_t q = a;
-    for (uint32_t c : r->crcs) {
-        const uint64_t e = std::min(b, (q / P + 1) * P);
-        const uint64_t pi = q / P;
-        if (q % P == 0) {
-            if (s->sums.size() <= pi) s->sums.resize(pi + 1);
-            s->sums[pi] = c;
-        } else if (pi < s->sums.size()) {
-            s->sums[pi] = gf2_mulmod(s->sums[pi], x8n(e - q, x8().v)) ^ c;
-        } else {  // a continuation with no start: never expected in submission order
-            s->fold_broken = true;
-            s->fold_stop = true;
-            return;
-        }
-        q = e;
+    if (!em::fold(s->sums, r->off, r->len, r->P, r->crcs.data(), r->crcs.size(), x8().v)) {
+        // a continuation with no start: never expected in submission order
+        s->fold_broken = true;
+        s->fold_stop = true;
     }
 }
 
