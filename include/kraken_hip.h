@@ -281,7 +281,7 @@ int krk_sha256_host(const uint8_t* const* data_host, const uint64_t* lengths, ui
  *
  * Placement, fixed at creation:
  *   KRK_PLACE_GPU   bytes go through the device's submission engine: the caller copies
- *                   them into pooled pinned slots (512 KiB, KRK_SLOT_KB) and every
+ *                   them into pooled pinned slots (512 KiB) and every
  *                   pending slot of every GPU digester of the device is digested in
  *                   ONE multi-stream sha256_multi launch (a dispatcher thread batches
  *                   them).  A digester's midstate lives in an HBM row of the engine,

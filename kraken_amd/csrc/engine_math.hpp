@@ -1,8 +1,8 @@
-// engine_math.hpp -- the submission engine's piece arithmetic (engine.cpp): how a CRC request
+// engine_math.hpp -- the submission engine's piece arithmetic: how a CRC request
 // over stream bytes [a, a + len) is cut at the multiples of the piece length (portions(), what
-// launch_crc lays out as items and runs), and how the portions' CRCs, each hashed as an
+// launch_crc of engine.cpp lays out as items and runs), and how the portions' CRCs, each hashed as an
 // independent message, fold back into the stream's piece sums in submission order (fold(), what
-// stream_fold runs on the completer thread).  On finalised IEEE sums (crc_math.hpp)
+// stream_fold of piece_stream.cpp runs on the completer thread).  On finalised IEEE sums (crc_math.hpp)
 //     crc(A || B) = shift(crc(A), |B|) ^ crc(B),      shift(c, n) = c * x^(8n) mod P,
 // so a portion that starts a piece sets the piece's sum and one that continues a piece shifts the
 // sum by its own length and XORs its CRC in.  Header-only and free of the runtime, so that

@@ -5,7 +5,7 @@
 // I/O mode, placement pins, start-up calibration and trace output.  The production library
 // reads these only (tests/test_capi_cpu.py checks its strings against the table).
 // KRK_AB_ENV: the A/B switches of measurement sessions (kernel and layout variants, thread
-// hand-outs, slot sources, ISA fallbacks, fault injection).  Read by the diag build
+// hand-outs, ISA fallbacks, fault injection).  Read by the diag build
 // (`make diag`, KRK_DIAG) only; the production library keeps each one's measured default and
 // does not even hold the name (every such switch forked the product
 // path, and untested combinations grew with each round).

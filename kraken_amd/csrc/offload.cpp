@@ -29,10 +29,6 @@
 
 namespace krk {
 
-void host_sha256_blocks(uint32_t h[8], const uint8_t* p, size_t nblocks);
-void host_sha256_final(const uint32_t h[8], uint64_t absorbed, const uint8_t* tail, size_t n, uint8_t out[32]);
-uint32_t host_crc32_update(uint32_t crc, const uint8_t* p, size_t n);
-
 // One host thread, bytes/s: measured once (16 MiB) and derated for the clock a fully
 // loaded socket holds.  SHA-256 (x86 SHA extensions) and the piece CRC (PCLMUL folding).
 constexpr double kHostDerate = 0.85;
@@ -332,7 +328,7 @@ Rates planner_rates(Device* D) {
 // pinned H2D rate (C2 end-to-end 45.7-54.4 GB/s against 54 GB/s pinned).
 double host_link(const Rates& R) { return 0.85 * R.h2d; }
 
-// The AUTO Digester crossover (engine.cpp host_stream_limit): m live digesters on the
+// The AUTO Digester crossover (digester.cpp host_stream_limit): m live digesters on the
 // host run SHA-NI on their writers' threads, min(m, threads) x one thread's rate; on the
 // GPU their pending slots are coalesced into multi-stream launches that read the pinned
 // slots in place, m x the tier's per-stream rate (x kEngineEff: the engine's launches

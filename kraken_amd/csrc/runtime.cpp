@@ -40,7 +40,6 @@ void set_error(int code, const char* fmt, ...) {
     if (code == KRK_EHIP || code == KRK_ENOMEM) (void)hipGetLastError();
 }
 
-void engine_teardown(Device& D);                 // engine.cpp
 void set_device_set_from_mask(uint64_t mask);    // multidev.cpp
 
 // Everything a device context holds: streams, tables, scratch cache, pinned

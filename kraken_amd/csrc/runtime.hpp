@@ -1,7 +1,7 @@
 // runtime.hpp -- internal to libkraken_hip: device contexts, the stream-ordered
 // scratch cache, the CRC work builder and the SHA job runner shared by the C ABI
 // (runtime.cpp, batch_dev.cpp, info_hash_dev.cpp, crc_host.cpp, placement.cpp, windows.cpp) and the
-// submission engine (engine.cpp).  Not part of the ABI.
+// submission engine (engine.hpp, engine.cpp).  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <sched.h>
@@ -140,58 +140,6 @@ inline void drain_timing() {
     }
     g_pending.clear();
     hipSetDevice(cur);
-}
-
-// ------------------------------------------------------------------ NUMA
-// NUMA node of device `id` (its PCI function's sysfs entry); -1 if unknown.
-inline int device_numa_node(int id) {
-    char bus[64] = {0};
-    if (hipDeviceGetPCIBusId(bus, sizeof bus, id) != hipSuccess) return -1;
-    for (char* c = bus; *c; ++c) *c = (char)tolower(*c);
-    std::string path = std::string("/sys/bus/pci/devices/") + bus + "/numa_node";
-    FILE* f = fopen(path.c_str(), "r");
-    if (!f) return -1;
-    int node = -1;
-    if (fscanf(f, "%d", &node) != 1) node = -1;
-    fclose(f);
-    return node;
-}
-
-// The CPUs of NUMA node `node` this process may run on (empty if none / unknown).
-inline cpu_set_t numa_node_cpus(int node) {
-    cpu_set_t s, allowed;
-    CPU_ZERO(&s);
-    if (node < 0 || sched_getaffinity(0, sizeof allowed, &allowed) != 0) return s;
-    std::string path = "/sys/devices/system/node/node" + std::to_string(node) + "/cpulist";
-    FILE* f = fopen(path.c_str(), "r");
-    if (!f) return s;
-    char buf[4096] = {0};
-    if (!fgets(buf, sizeof buf, f)) buf[0] = 0;
-    fclose(f);
-    for (char* p = strtok(buf, ",\n"); p; p = strtok(nullptr, ",\n")) {
-        int a = 0, b = 0;
-        const int k = sscanf(p, "%d-%d", &a, &b);
-        if (k < 1) continue;
-        if (k == 1) b = a;
-        for (int c = a; c <= b && c < CPU_SETSIZE; ++c)
-            if (CPU_ISSET(c, &allowed)) CPU_SET(c, &s);
-    }
-    return s;
-}
-
-// f() on the calling thread bound to the CPUs of NUMA node `node` (memory it allocates or
-// first touches comes from that node under the default local policy), then the thread's
-// affinity restored.  node < 0, or no allowed CPU there: f() as is.
-template <class F>
-inline void on_numa_node(int node, F&& f) {
-    cpu_set_t want = numa_node_cpus(node), old;
-    if (node < 0 || CPU_COUNT(&want) == 0 || pthread_getaffinity_np(pthread_self(), sizeof old, &old) != 0 ||
-        pthread_setaffinity_np(pthread_self(), sizeof want, &want) != 0) {
-        f();
-        return;
-    }
-    f();
-    pthread_setaffinity_np(pthread_self(), sizeof old, &old);
 }
 
 // ------------------------------------------------------------------ device
@@ -791,7 +739,11 @@ int host_cpu_budget();
 // with its share of the budget, so N devices' workers do not start N x 16 copy threads.
 inline thread_local int t_host_share = 0;
 inline int host_threads_for_call() { return t_host_share > 0 ? t_host_share : host_cpu_budget(); }
-uint32_t host_crc32_update(uint32_t crc, const uint8_t* p, size_t n);  // host_meta.cpp
+// One thread's hashes (host_meta.cpp): h over whole blocks; the digest of h, `absorbed` bytes
+// in, over the last n bytes; crc32.Update.
+void host_sha256_blocks(uint32_t h[8], const uint8_t* p, size_t nblocks);
+void host_sha256_final(const uint32_t h[8], uint64_t absorbed, const uint8_t* tail, size_t n, uint8_t out[32]);
+uint32_t host_crc32_update(uint32_t crc, const uint8_t* p, size_t n);
 // One host thread's rates, bytes/s, each measured once per process on 16 MiB (offload.cpp;
 // no device needed): SHA-256 (x86 SHA extensions), CRC-32 (PCLMUL folding), memcpy.
 double host_sha_rate();
@@ -827,7 +779,7 @@ uint32_t crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
 // crc32.Update(crc, p[0, n)) with idle pool threads taking spans of a large buffer.
 uint32_t host_crc32_update_par(uint32_t crc, const uint8_t* p, size_t n);
 // The placement (KRK_PLACE_HOST / KRK_PLACE_GPU) of a CRC-only call asked for `placement`
-// (engine.cpp): AUTO follows krk_set_crc_placement, then the measured host-vs-link
+// (piece_stream.cpp): AUTO follows krk_set_crc_placement, then the measured host-vs-link
 // crossover; -1 with *rc set when GPU is forced and no device is usable.
 int resolve_crc_placement(int placement, int* rc);
 double host_link(const Rates& R);
@@ -870,6 +822,8 @@ int info_hash_dev(Device* D, const int64_t* piece_lengths, const uint32_t* sums_
 // What KRK_PLACE_AUTO resolves to for krk_metainfo_batch_dev's InfoHash (info_hash_dev.cpp):
 // KRK_PLACE_HOST or KRK_PLACE_GPU.
 int info_hash_placement_resolved();
+int place_device();  // multidev.cpp: next device of the process's device set
+void engine_teardown(Device& D);  // krk_shutdown: the submission engine's threads, queues and slots (engine.cpp)
 void owner_tables_teardown(Device& D);  // krk_shutdown: the cached owner tables (placement.cpp)
 void offload_teardown(Device& D);  // krk_shutdown: the offload threads' streams and pinned buffers
 void offload_hash_host(const std::vector<const uint8_t*>& ptrs, const std::vector<uint64_t>& lens, int threads,

@@ -1,12 +1,13 @@
-"""The submission engine (kraken_amd/csrc/engine.cpp) at its slot, block and piece edges: the
+"""The submission engine (kraken_amd/csrc/engine.cpp, with digester.cpp and piece_stream.cpp on
+top of it) at its slot, block and piece edges: the
 write plans, their references from hashlib and zlib, and the runner over the C ABI, shared by
 tests/test_gpu_engine_matrix.py (KRK_PLACE_GPU: the engine's slot requests, state rows, portions
 and fold) and tests/test_engine_matrix_cpu.py (KRK_PLACE_HOST: the same plans through
 host_meta.cpp's tail buffer and the host piece loop, no device).  A helper module, not a test file.
 
 S = 524288 is the engine's slot, B = 64 a SHA-256 block, I = 262144 kItemBytes of kernels.hpp,
-Q = 8 the requests an owner keeps in flight (the production library reads no switch that changes
-them).  All data is views into ONE seeded arena; every comparison is bit-exact over every output.
+Q = 8 the requests an owner keeps in flight (kSlotBytes and kOwnerInflight of engine.hpp: constants,
+no switch changes them).  All data is views into ONE seeded arena; every comparison is bit-exact over every output.
 
 A plan is a list of steps -- ("w", n) a write of n bytes, ("z", null) a zero-length write with a
 NULL or a non-NULL buffer, ("s",) a sum -- over the view [off, off + total).  Every sum is compared

@@ -1,5 +1,5 @@
 // The submission engine's piece arithmetic (kraken_amd/csrc/engine_math.hpp: what launch_crc
-// and stream_fold of engine.cpp run) as a stand-alone program:
+// of engine.cpp and stream_fold of piece_stream.cpp run) as a stand-alone program:
 //  1. portions() over an exhaustive small space against a walk over the bytes;
 //  2. fold() over real bytes cut into requests at every structural position, every portion's CRC
 //     from an in-program bitwise CRC-32, every piece sum against the bitwise CRC of the piece;

@@ -844,7 +844,8 @@ def test_production_library_reads_only_the_operator_knobs():
     """the production library's environment is INTEGRATION.md's operator
     table, exactly -- every KRK_* name in its strings is in the table and every table entry is
     one it reads; the A/B switches of measurement sessions (knobs.hpp KRK_AB_ENV) are read by
-    the diag build only.  Every library source reads its environment through knobs.hpp."""
+    the diag build only, and INTEGRATION.md's A/B paragraph names exactly those.  Every library
+    source reads its environment through knobs.hpp."""
     import glob
     import os
     import re
@@ -869,3 +870,7 @@ def test_production_library_reads_only_the_operator_knobs():
     op = set(re.findall(r'KRK_OP_ENV\("(KRK_[A-Z0-9_]+)"\)', src))
     ab = set(re.findall(r'KRK_AB_ENV\("(KRK_[A-Z0-9_]+)"\)', src))
     assert op == table and not op & ab, (sorted(op ^ table), sorted(op & ab))
+    # the A/B paragraph after the table lists exactly the switches the sources read
+    c = doc.index("does not hold the name:", a)
+    listed = set(re.findall(r"`(KRK_[A-Z0-9_]+)`", doc[c:doc.index("\n\n", c)]))
+    assert ab == listed, ("read, not listed", sorted(ab - listed), "listed, not read", sorted(listed - ab))

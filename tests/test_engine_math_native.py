@@ -1,5 +1,6 @@
 """tests/native/engine_math_main.cpp: the submission engine's piece arithmetic
-(kraken_amd/csrc/engine_math.hpp, what launch_crc and stream_fold of engine.cpp run) as a
+(kraken_amd/csrc/engine_math.hpp, what launch_crc of engine.cpp and stream_fold of
+piece_stream.cpp run) as a
 stand-alone CPU program (its own main, nothing of the library linked) built with AddressSanitizer
 and UndefinedBehaviorSanitizer and run directly."""
 import os

@@ -1,4 +1,4 @@
-"""The submission engine behind the streaming entry points (engine.cpp): concurrent
+"""The submission engine behind the streaming entry points (engine.cpp, digester.cpp, piece_stream.cpp): concurrent
 Digesters / piece streams / crc32.Update calls coalesced into multi-stream launches,
 pooled pinned staging, per-owner ordering; the host crossovers.  Reference callers:
 origin/blobserver/uploader.go:75 and lib/store/ca_store.go:119 (a Digester per upload /
@@ -19,7 +19,7 @@ from kraken_amd._capi import KRK_PLACE_AUTO, KRK_PLACE_GPU, KRK_PLACE_HOST, chec
 
 pytestmark = pytest.mark.gpu
 
-SLOT = 512 << 10  # the engine's default slot (KRK_SLOT_KB)
+SLOT = 512 << 10  # the engine's slot (kSlotBytes, engine.hpp)
 
 
 def _stats():

@@ -1,4 +1,4 @@
-"""GPU parity: the submission engine (engine.cpp) at its slot, block and piece edges, bit-exact
+"""GPU parity: the submission engine (engine.cpp, digester.cpp, piece_stream.cpp) at its slot, block and piece edges, bit-exact
 against hashlib and zlib (the plans, the references and the runner live in tests/engine_matrix.py):
 
 1. groups A to D in process on KRK_PLACE_GPU -- Digester tails, splits around the slot and sums at
