@@ -1,6 +1,7 @@
 // batch_dev.cpp -- the C ABI's device-resident batch calls: piece sums, SHA-256 with its host
 // share and tail handoff, the fused metainfo + digest batch, the chunk (window) steps and
 // piece verification over blobs already in HBM.
+#include "offload.hpp"
 #include "runtime.hpp"
 #include "staging.hpp"
 

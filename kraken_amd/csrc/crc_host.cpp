@@ -9,6 +9,7 @@
 #include <chrono>
 #include <optional>
 
+#include "offload.hpp"
 #include "runtime.hpp"
 #include "staging.hpp"
 

@@ -5,6 +5,7 @@
 // (host_meta.cpp).  Beyond it a digester owns a state row of its device's submission engine
 // (engine.cpp) and hands it its bytes a slot at a time.
 #include "engine.hpp"
+#include "offload.hpp"
 
 namespace krk {
 namespace {
@@ -15,7 +16,7 @@ std::atomic<int64_t> g_host_streams{-1};  // -1: default (host threads x per-str
 // Live digesters up to which new ones run on their caller's thread: below the crossover
 // where the GPU engine's aggregate (live streams x the planner's per-stream rate, capped by
 // the host link) overtakes the host's (the CPU budget x one thread's SHA-NI rate), both
-// from the calling thread's device's planner rates (offload.cpp digester_crossover; the
+// from the calling thread's device's planner rates (planner_math.hpp digester_crossover; the
 // nominal ones without a device).  KRK_DIGESTER_HOST_STREAMS / krk_set_digester_host_streams
 // pin it.
 int64_t host_stream_limit() {

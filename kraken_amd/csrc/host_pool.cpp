@@ -10,6 +10,8 @@
 // nothing left -- and concurrent callers each keep at least their own thread.  CRC-32 is
 // linear over GF(2), so a buffer cut into spans is hashed span by span on any threads and
 // recombined in order: crc(A||B) = crc(A) * x^(8|B|) ^ crc(B) (crc_math.hpp).
+#include <sched.h>
+
 #include <condition_variable>
 #include <deque>
 #include <functional>
@@ -28,6 +30,52 @@ struct HostJob {
     size_t done = 0;  // under mu
     int want = 0;     // helpers still wanted (under the pool's mu)
 };
+
+// ------------------------------------------------------------------ CPU budget
+// The node's CPUs as this process sees them: its affinity mask capped by the cgroup v2 CPU
+// quota (the GPU boxes expose the whole machine in the mask but grant a share of it).
+static int node_cpu_count() {
+    cpu_set_t set;
+    int c = sched_getaffinity(0, sizeof set, &set) == 0 ? std::max(1, CPU_COUNT(&set))
+                                                        : (int)std::max(1u, std::thread::hardware_concurrency());
+    if (FILE* f = fopen("/sys/fs/cgroup/cpu.max", "r")) {  // "<quota> <period>" or "max <period>"
+        char q[32] = {0};
+        long long per = 0;
+        if (fscanf(f, "%31s %lld", q, &per) == 2 && strcmp(q, "max") != 0 && per > 0)
+            c = std::min<int>(c, std::max<long long>(1, atoll(q) / per));
+        fclose(f);
+    }
+    return c;
+}
+
+static int env_pos(const char* e) { return e && atoi(e) > 0 ? atoi(e) : 0; }
+
+struct CpuBudget {
+    int cpus, node;
+    const char* source;
+};
+
+// One process per GPU (origin/cmd/cmd.go:164 runs one origin a host; bench.py and
+// torch.distributed.run start one rank a GPU): the ranks of a node share its CPUs.
+//   KRK_HOST_CPUS            an operator's explicit per-process budget;
+//   LOCAL_WORLD_SIZE > 1     the node's CPUs / the ranks on it -- a launcher's
+//                            OMP_NUM_THREADS (torch.distributed.run sets 1 a rank) is
+//                            about OpenMP pools, not this library's hash threads;
+//   otherwise                the node's CPUs, capped by OMP_NUM_THREADS when set.
+static const CpuBudget& cpu_budget() {
+    static const CpuBudget b = [] {
+        const int node = node_cpu_count();
+        if (int x = env_pos(KRK_OP_ENV("KRK_HOST_CPUS"))) return CpuBudget{x, node, "KRK_HOST_CPUS"};
+        if (int w = env_pos(getenv("LOCAL_WORLD_SIZE")); w > 1)
+            return CpuBudget{std::max(1, node / w), node, "node/LOCAL_WORLD_SIZE"};
+        if (int o = env_pos(getenv("OMP_NUM_THREADS")); o > 0 && o < node)
+            return CpuBudget{o, node, "OMP_NUM_THREADS"};
+        return CpuBudget{node, node, "node"};
+    }();
+    return b;
+}
+
+int host_cpu_budget() { return cpu_budget().cpus; }
 
 // ------------------------------------------------------------------ CPU tokens
 // At most host_cpu_budget() threads run host hash work at once, whoever calls: 64 uploads'
@@ -191,3 +239,11 @@ uint32_t host_crc32_update_par(uint32_t crc, const uint8_t* p, size_t n) {
 }
 
 }  // namespace krk
+
+extern "C" int krk_host_cpu_budget(int* cpus, int* node_cpus, char* source, uint32_t cap) {
+    const krk::CpuBudget& b = krk::cpu_budget();
+    if (cpus) *cpus = b.cpus;
+    if (node_cpus) *node_cpus = b.node;
+    if (source && cap) snprintf(source, cap, "%s", b.source);
+    return KRK_OK;
+}

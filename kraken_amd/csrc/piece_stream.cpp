@@ -9,6 +9,7 @@
 // write); product code (host_meta.cpp).
 #include "engine.hpp"
 #include "engine_math.hpp"
+#include "offload.hpp"
 
 using namespace krk;
 

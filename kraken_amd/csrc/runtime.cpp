@@ -20,6 +20,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "offload.hpp"
 #include "runtime.hpp"
 #include "staging.hpp"
 

@@ -23,6 +23,7 @@
 #include "crc_math.hpp"
 #include "kernels.hpp"
 #include "knobs.hpp"
+#include "planner_math.hpp"
 
 namespace krk {
 
@@ -250,7 +251,7 @@ struct Device {
     // race the HIP runtime's own teardown.
     Pipeline* staging = nullptr;
     std::mutex staging_mu;
-    // Host threads + pinned double buffers of the SHA-256 host offload (offload.cpp).
+    // Host threads + pinned buffers of the SHA-256 host offload, the planner calibration (offload.cpp).
     OffloadPool* offload = nullptr;
     std::mutex offload_mu;
     // The 65,536 ShardID keys (2 bytes each) of the Locations shard table, uploaded
@@ -702,36 +703,7 @@ inline ShaJob full_job(const void* p, uint64_t len, uint32_t out) {
     return j;
 }
 
-
-
-// SHA-256 host offload (offload.cpp): the longest blobs of a batch hashed on host threads
-// while the GPU hashes the rest (krk_set_sha_host_offload).  Where the batch lives
-// decides what the host saves:
-//  * kOffDevice: blobs in HBM; the host reads its blobs out over D2H, the GPU still
-//    computes every piece CRC (krk_sha256_dev, krk_metainfo_digest_dev);
-//  * kOffHostSha: blobs in host memory, digests only; the host's blobs are hashed in place
-//    and never uploaded (krk_sha256_host);
-//  * kOffHostWhole: blobs in host memory, digests and piece sums; the host's blobs are
-//    hashed AND piece-summed in place and never uploaded (krk_metainfo_digest_host) --
-//    the batch's bytes over the host link shrink by theirs.
-//  * kOffHostFiles: cache files (krk_metainfo_digest_files): a host blob is read once and
-//    hashed and piece-summed chunk by chunk on one host thread.
-enum OffMode { kOffDevice = 0, kOffHostSha = 1, kOffHostWhole = 2, kOffHostFiles = 3 };
-// Host threads the offload of a `mode` batch may use (krk_set_sha_host_offload; 0 = off).
-int offload_threads(int mode = kOffDevice);
-bool offload_auto();  // the offload's threads are KRK_OFFLOAD_AUTO (not set by the caller)
-// What the planners know about this box (offload.cpp): per-stream SHA-256 rate of each
-// AUTO tier at full residency (eight / two / one lane(s)), pinned D2H / H2D, one host
-// thread's SHA-256 and CRC-32; measured on the device at first use.
-struct Rates {
-    double stream[3];
-    double d2h, h2d, host_sha, host_crc, host_copy;
-    int cus;
-    int source;  // KRK_RATES_*
-};
-Rates planner_rates(Device* D);  // D == nullptr: the override or the nominal rates
-int calibrate_device(Device* D);  // (re)measure D's rates now (krk_init, krk_planner_calibrate)
-// Host CPUs this process may use (offload.cpp): KRK_HOST_CPUS, else the node's CPUs
+// Host CPUs this process may use (host_pool.cpp): KRK_HOST_CPUS, else the node's CPUs
 // (affinity capped by the cgroup quota) / LOCAL_WORLD_SIZE under a launcher, else the
 // node's capped by OMP_NUM_THREADS.
 int host_cpu_budget();
@@ -744,12 +716,6 @@ inline int host_threads_for_call() { return t_host_share > 0 ? t_host_share : ho
 void host_sha256_blocks(uint32_t h[8], const uint8_t* p, size_t nblocks);
 void host_sha256_final(const uint32_t h[8], uint64_t absorbed, const uint8_t* tail, size_t n, uint8_t out[32]);
 uint32_t host_crc32_update(uint32_t crc, const uint8_t* p, size_t n);
-// One host thread's rates, bytes/s, each measured once per process on 16 MiB (offload.cpp;
-// no device needed): SHA-256 (x86 SHA extensions), CRC-32 (PCLMUL folding), memcpy.
-double host_sha_rate();
-double host_crc_rate();
-double host_copy_rate();
-
 // The process's host worker pool (host_pool.cpp, host_cpu_budget() - 1 threads).  A batch
 // of n items runs on up to `helpers` pool threads idle at construction and on the thread
 // that calls join() (which returns once all n are done; the destructor joins).  Items are
@@ -782,34 +748,6 @@ uint32_t host_crc32_update_par(uint32_t crc, const uint8_t* p, size_t n);
 // (piece_stream.cpp): AUTO follows krk_set_crc_placement, then the measured host-vs-link
 // crossover; -1 with *rc set when GPU is forced and no device is usable.
 int resolve_crc_placement(int placement, int* rc);
-double host_link(const Rates& R);
-// GPU-placed digesters' modelled aggregate for m live streams, and the AUTO Digester
-// crossover: the fewest live digesters whose GPU aggregate beats `threads` host SHA-NI
-// threads (INT64_MAX: never) -- offload.cpp.
-double engine_gpu_bps(uint64_t m, const Rates& R);
-int64_t digester_crossover(const Rates& R, int threads);
-std::vector<uint32_t> offload_plan(const uint64_t* lens, uint64_t n, int threads, const Rates& R, double* gpu_s,
-                                   double* host_s, int mode = kOffDevice);
-// Tail handoff of device-resident chains (offload.cpp): chain idx[k] runs its first start[k]
-// bytes on the GPU (0: none) and the rest on a host thread from the GPU's midstate; listed in
-// the order of start (the host threads' queue).  end_s = the planned batch end, gpu_s = the
-// GPU alone; empty when host takeovers would not end the batch sooner.
-struct TailPlan {
-    std::vector<uint32_t> idx;
-    std::vector<uint64_t> start;
-    double gpu_s = 0, end_s = 0;
-};
-TailPlan tail_plan(const uint64_t* lens, uint64_t n, int threads, const Rates& R);
-// Where the host threads' chains start (offload_hash): chain j from byte start[j], from the
-// GPU's midstate at note + 8 * slot[j] once the GPU has written it there (all eight words
-// off kTailSentinel, or gpu_done complete), from the IV when start[j] == 0.
-constexpr uint32_t kTailSentinel = 0xFFFFFFFFu;
-struct TailSrc {
-    const volatile uint32_t* note;
-    const uint32_t* slot;
-    const uint64_t* start;
-    hipEvent_t gpu_done;
-};
 // Where a kernel may write [p, p + n): device memory, or page-locked host memory the GPU maps
 // at its host address (placement.cpp).
 bool device_writable(const void* p, uint64_t n);
@@ -825,21 +763,5 @@ int info_hash_placement_resolved();
 int place_device();  // multidev.cpp: next device of the process's device set
 void engine_teardown(Device& D);  // krk_shutdown: the submission engine's threads, queues and slots (engine.cpp)
 void owner_tables_teardown(Device& D);  // krk_shutdown: the cached owner tables (placement.cpp)
-void offload_teardown(Device& D);  // krk_shutdown: the offload threads' streams and pinned buffers
-void offload_hash_host(const std::vector<const uint8_t*>& ptrs, const std::vector<uint64_t>& lens, int threads,
-                       uint8_t* out);
-// kOffHostWhole: blob j's digest to out + 32 j and its piece sums (piece length plen[j])
-// to sums[j][0 .. ceil(len / plen)), on up to `threads` threads; the SHA-256 pass and the
-// CRC pass of a blob are separate tasks, longest first.
-void offload_whole_host(const std::vector<const uint8_t*>& ptrs, const std::vector<uint64_t>& lens,
-                        const std::vector<uint64_t>& plen, const std::vector<uint32_t*>& sums, int threads,
-                        uint8_t* out);
-int offload_whole_files(const std::vector<const char*>& paths, const std::vector<uint64_t>& lens,
-                        const std::vector<uint64_t>& plen, const std::vector<uint32_t*>& sums, int threads,
-                        uint8_t* out);
-int offload_hash(Device* D, const std::vector<const uint8_t*>& ptrs, const std::vector<uint64_t>& lens, int threads,
-                 hipEvent_t ready, uint8_t* out, const TailSrc* tail = nullptr);
-int offload_store(Device* D, const std::vector<uint32_t>& idx, const uint8_t* dig, uint8_t* digests_dev,
-                  hipStream_t s);
 
 }  // namespace krk

@@ -24,6 +24,7 @@
 #include <thread>
 
 #include "host_register.hpp"
+#include "offload.hpp"
 #include "runtime.hpp"
 #include "staging.hpp"
 

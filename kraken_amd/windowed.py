@@ -335,7 +335,7 @@ class WindowedRun:
 # takes ~18 s at ~58 MB/s a stream while the shard's 1.47 TB would take ~2 s -- ends when
 # that chain ends.  Host threads (SHA-NI, ~2.3 GB/s, 40x a GPU stream) steal chains instead:
 # at each window boundary every thread that will be free before the next window ends takes
-# the chain with the most bytes left (earliest deadline first, as offload.cpp tail_plan does
+# the chain with the most bytes left (earliest deadline first, as planner_math.hpp tail_plan does
 # for batches in HBM), from the midstate the windows keep in HBM (ChunkedBatch.state); the
 # chain leaves the window schedule (krk_window_sched_drop), its remaining bytes are
 # generated on the device in 64 MiB pieces, their piece CRCs run on the GPU
@@ -363,7 +363,7 @@ TAIL_FIRST_PIECE = 8 << 20  # a stolen chain's first piece (a multiple of 64)
 
 def tail_thread_rate(rates, threads):
     """One tail thread's bytes/s: its SHA-NI rate (the planner's figure is derated 15 % for a
-    loaded socket; a tail thread alone on its buffers loses ~2 %, offload.cpp tail_plan),
+    loaded socket; a tail thread alone on its buffers loses ~2 %, planner_math.hpp tail_plan),
     capped by its share of the device-to-host copy rate."""
     return min(rates["host_sha_bps"] * (0.98 / 0.85), rates["d2h_bps"] / max(1, int(threads)))
 

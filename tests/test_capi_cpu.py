@@ -679,7 +679,7 @@ def _replay_tails(lens, idx, start, threads, r, h):
 
 
 def test_sha_tail_plan_follows_rates():
-    """Tail handoff of the host offload (offload.cpp tail_plan): every chain starts on the GPU
+    """Tail handoff of the host offload (planner_math.hpp tail_plan): every chain starts on the GPU
     and host threads finish the tails of the longest from the GPU's midstate.  C2's shape on
     16 threads at the box's rates (58.5 MB/s a GPU stream, 2.1 GB/s a SHA-NI thread as the
     planner reports it -- derated 15 %; a tail thread is priced at 0.98 of the rate measured,
@@ -696,7 +696,7 @@ def test_sha_tail_plan_follows_rates():
         assert 1.38 < end_s < 1.47 and abs(gpu_s - 104857600 / 58.5e6) < 1e-6, (end_s, gpu_s)
         assert (start % 64 == 0).all() and (start < 104857600).all() and (np.diff(start.astype(np.int64)) >= 0).all()
         assert (start[:16] == 0).all() and start[-1] > 0  # the first takeovers are whole blobs
-        h = 2.1e9 * 0.98 / 0.85  # a tail thread's rate (offload.cpp tail_plan)
+        h = 2.1e9 * 0.98 / 0.85  # a tail thread's rate (planner_math.hpp tail_plan)
         assert _replay_tails(L, idx, start, 16, 58.5e6, h) <= end_s * 1.001
         idx, start, end_s, gpu_s = Dv.sha_tail_plan([1 << 30] + [1 << 20] * 5, 16)
         assert 0 in idx.tolist() and start[idx.tolist().index(0)] == 0 and end_s < 0.6

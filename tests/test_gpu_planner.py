@@ -1,4 +1,4 @@
-"""The planners' rates measured on the device (krk_planner_rates_get, offload.cpp
+"""The planners' rates measured on the device (krk_planner_rates_get, rates.cpp
 calibrate): each SHA-256 tier's per-stream rate at full residency, pinned copy rates,
 one host thread's SHA-256 / CRC-32 rates -- and the offload plan of a device batch
 priced with them."""

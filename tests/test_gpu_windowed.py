@@ -132,12 +132,21 @@ def test_tail_handoff_matches_one_shot_and_oracle(one_shot, orc, cap, threads, p
 
 def test_sha256_resume_from_device_bytes(gpu, orc):
     """krk_sha256_resume_dev_on_host: one chain continued on the calling thread from device
-    bytes, in runs of whole blocks then a final run of any length (0, 1, 55, 56, 64, 8 MiB +
-    3 ...), equals hashlib over the whole blob."""
+    bytes, in runs of whole blocks (ending at `cuts`) then a final run of any length (0, 1, 55,
+    56, 64, 8 MiB + 3 ...), equals hashlib over the whole blob.  The copies come down in 8 MiB
+    chunks through a ring of four buffers: 5 chunks + 3 B in one run wrap the ring, a non-final
+    run of exactly 4 chunks (and of 4 chunks + 64 B) fills it and leaves an empty (a 1 B) final
+    run; the last case passes a stream, so the copies wait for an event recorded on it."""
     import ctypes as C
     from kraken_amd.windowed import _IV
-    for L, cuts in ((0, []), (1, []), (55, []), (64, []), (128, [64]), (130, [64]), ((8 << 20) + 3, [1 << 20, 3 << 20]),
-                    ((17 << 20) + 64, [64, (16 << 20) + 64])):
+    M = 1 << 20
+    st = C.c_void_p()
+    D.check(D.lib.krk_stream_create(C.byref(st)))
+    for L, cuts, stream in ((0, [], None), (1, [], None), (55, [], None), (64, [], None), (128, [64], None),
+                            (130, [64], None), (8 * M + 3, [1 * M, 3 * M], None),
+                            (17 * M + 64, [64, 16 * M + 64], None), (40 * M + 3, [], None),
+                            (32 * M, [32 * M], None), (32 * M + 65, [32 * M + 64], None),
+                            (17 * M + 64, [64, 16 * M + 64], st)):
         data = orc.synth(4242 + L, L)
         buf = D.DeviceBuffer(max(L, 1))
         if L:
@@ -145,10 +154,12 @@ def test_sha256_resume_from_device_bytes(gpu, orc):
         h = _IV.copy()
         out = np.zeros(32, np.uint8)
         prev = 0
-        for c in cuts + [L]:
+        runs = cuts + [L]
+        for k, c in enumerate(runs):
             D.check(D.lib.krk_sha256_resume_dev_on_host(h.ctypes.data_as(C.POINTER(C.c_uint32)), prev,
-                                                        C.c_void_p(buf.ptr + prev), c - prev, int(c == L),
-                                                        out.ctypes.data_as(C.POINTER(C.c_uint8)), None))
+                                                        C.c_void_p(buf.ptr + prev), c - prev, int(k == len(runs) - 1),
+                                                        out.ctypes.data_as(C.POINTER(C.c_uint8)), stream))
             prev = c
-        assert bytes(out) == hashlib.sha256(data.tobytes()).digest(), L
+        assert bytes(out) == hashlib.sha256(data.tobytes()).digest(), (L, cuts)
         buf.free()
+    D.check(D.lib.krk_stream_destroy(st))
