@@ -74,6 +74,21 @@ uint64_t krk_num_pieces(uint64_t length, int64_t piece_length);
  * Give each call its own span. */
 int krk_piece_sums_dev(const krk_blob* blobs, uint64_t n_blobs, uint32_t* sums_dev, void* stream);
 
+/* Host forms (sums_host: krk_piece_sums_host, krk_piece_sums_files, krk_metainfo_digest_host,
+ * krk_metainfo_digest_files): the same span, and the same advice -- give each call its own.
+ * Every blob's own words are written, words outside the span are never touched, and a batch
+ * with no piece at all writes nothing (sums_host may then be NULL).  A word in a GAP inside
+ * the span belongs to the call and comes back either zero or as the caller left it,
+ * depending on where the sums were computed:
+ *   krk_metainfo_digest_host, krk_metainfo_digest_files   zero (the device span is copied back;
+ *                                                         the host offload's blobs are then
+ *                                                         written over their own words)
+ *   krk_piece_sums_files, CRC placement GPU               zero (the same copy)
+ *   krk_piece_sums_files, CRC placement HOST              untouched (threads write their pieces)
+ *   krk_piece_sums_host                                   untouched, whatever its GPU share
+ * Do not keep anything in a gap.  tests/test_gpu_window_matrix.py and
+ * tests/test_window_matrix_cpu.py pin each row but the third. */
+
 /* Host batch (end-to-end): blobs[i].data are HOST pointers; sums_host receives
  * the sums.  Streams bytes through pinned staging, overlapping H2D with the
  * kernel.  Synchronous.  This is the batch form of Generator.Generate's

@@ -13,6 +13,7 @@
 #include <unordered_map>
 
 #include "runtime.hpp"
+#include "window_math.hpp"
 
 namespace krk {
 
@@ -299,22 +300,18 @@ inline void par_copy(const std::vector<CopyTask>& tasks) {
     size_t total = 0;
     for (const auto& t : tasks) total += t.n;
     const unsigned T = copy_threads();
-    if (T == 1 || total < (8u << 20)) {
+    if (T == 1 || total < kSplitMinBytes) {
         for (const auto& t : tasks) memcpy(t.dst, t.src, t.n);
         return;
     }
-    // Cut the concatenated byte range into T equal spans.
+    // Cut the concatenated byte range into T equal spans (window_math.hpp).
     auto run = [&](size_t lo, size_t hi) {
-        size_t pos = 0;
-        for (const auto& t : tasks) {
-            const size_t a = std::max(lo, pos), b = std::min(hi, pos + t.n);
-            if (a < b) memcpy(t.dst + (a - pos), t.src + (a - pos), b - a);
-            pos += t.n;
-            if (pos >= hi) break;
-        }
+        cut_span(
+            tasks.size(), [&](size_t i) { return tasks[i].n; }, lo, hi, false,
+            [&](size_t i, size_t a, size_t b) { memcpy(tasks[i].dst + a, tasks[i].src + a, b - a); });
     };
     // spans on the calling thread and the host pool's idle threads
-    const size_t span = (total + T - 1) / T;
+    const size_t span = copy_span_bytes(total, T);
     host_parallel_for(T, (int)T - 1, [&](size_t i) { run(i * span, std::min(total, (i + 1) * span)); });
 }
 
@@ -351,20 +348,16 @@ inline uint64_t file_readahead_bytes() {
 inline long par_read(const std::vector<ReadTask>& tasks, bool direct, int* err) {
     // Spans are cut in a stream of the tasks laid end to end, each padded to 4 KiB
     // when direct, so every span boundary falls on a block boundary of its task.
-    auto padded = [direct](size_t n) { return direct ? (n + 4095) & ~size_t(4095) : n; };
     size_t total = 0;
-    for (const auto& t : tasks) total += padded(t.n);
+    for (const auto& t : tasks) total += span_padded(t.n, direct);
     std::atomic<long> bad{-1};
     std::atomic<int> bad_errno{0};
     const uint64_t R = direct ? 0 : file_readahead_bytes();
     auto run = [&](size_t lo, size_t hi) {
-        size_t pos = 0;
-        for (size_t i = 0; i < tasks.size() && pos < hi; pos += padded(tasks[i].n), ++i) {
+        bool failed = false;  // a failed read ends the span
+        auto read_piece = [&](size_t i, size_t a, size_t b) {
+            if (failed) return;
             const ReadTask& t = tasks[i];
-            size_t a = std::max(lo, pos), b = std::min(hi, pos + t.n);
-            if (a >= b) continue;
-            a -= pos;
-            b -= pos;
             if (R && t.ra) {  // keep the file hinted R bytes past this read, R bytes a hint
                 const uint64_t want = std::min(t.flen, t.off + b + R);
                 uint64_t mark = t.ra->load(std::memory_order_relaxed);
@@ -385,15 +378,16 @@ inline long par_read(const std::vector<ReadTask>& tasks, bool direct, int* err) 
                     long expect = -1;
                     bad.compare_exchange_strong(expect, (long)i);
                     bad_errno.store(got < 0 ? errno : 0);
+                    failed = true;
                     return;
                 }
                 a += (size_t)got;
             }
-        }
+        };
+        cut_span(tasks.size(), [&](size_t i) { return tasks[i].n; }, lo, hi, direct, read_piece);
     };
-    const unsigned T = (total < (8u << 20)) ? 1 : copy_threads();
-    constexpr size_t kAlign = size_t(1) << 20;
-    const size_t span = std::max(kAlign, ((total + T - 1) / T + kAlign - 1) & ~(kAlign - 1));
+    const unsigned T = (total < kSplitMinBytes) ? 1 : copy_threads();
+    const size_t span = read_span_bytes(total, T);
     const size_t spans = (total + span - 1) / span;
     host_parallel_for(spans, (int)spans - 1, [&](size_t i) { run(i * span, std::min(total, (i + 1) * span)); });
     *err = bad_errno.load();

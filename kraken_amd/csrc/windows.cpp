@@ -27,73 +27,11 @@
 #include "offload.hpp"
 #include "runtime.hpp"
 #include "staging.hpp"
+#include "window_math.hpp"
 
 namespace krk {
 
-// ----------------------------------------------------------------- the window schedule
-struct WinChunk {
-    uint32_t blob;
-    uint64_t off, len;
-};
-
-class WindowSched {
-  public:
-    // blobs: the windowed blobs' indices into lens; chunks a multiple of `align` bytes
-    // (64: SHA-256 blocks; 4 KiB for O_DIRECT file reads) except each blob's last.
-    WindowSched(const uint64_t* lens, std::vector<uint32_t> blobs, uint64_t W, uint64_t cap, uint64_t align = 64)
-        : L_(lens), W_(W), cap_(std::max<uint64_t>(cap, 1)), align_(std::max<uint64_t>(align, 64)), queue_(std::move(blobs)) {
-        std::stable_sort(queue_.begin(), queue_.end(), [&](uint32_t a, uint32_t b) { return L_[a] > L_[b]; });
-    }
-    // The next window's chunks (in admission order); false once every blob is done.
-    bool next(std::vector<WinChunk>& out) {
-        out.clear();
-        while (live_.size() < cap_ && q_ < queue_.size()) live_.push_back({queue_[q_++], 0});
-        if (live_.empty()) return false;
-        max_live_ = std::max<uint64_t>(max_live_, live_.size());
-        const uint64_t c = std::max(align_, std::min(max_chunk_, W_ / live_.size()) / align_ * align_);
-        size_t keep = 0;
-        for (size_t k = 0; k < live_.size(); ++k) {
-            auto [b, pos] = live_[k];
-            const uint64_t take = std::min(c, L_[b] - pos);
-            out.push_back({b, pos, take});
-            pos += take;
-            if (pos < L_[b]) live_[keep++] = {b, pos};
-        }
-        live_.resize(keep);
-        return true;
-    }
-    uint64_t max_live() const { return max_live_; }
-    // At most `c` bytes a chunk (rounded down to the alignment): the windows stay short once
-    // few blobs are live (the tail handoff hands chains over at window boundaries).
-    void set_max_chunk(uint64_t c) { max_chunk_ = std::max<uint64_t>(c, 1); }
-    // Take blob b out of the schedule (its chain continues elsewhere): a live blob's slot goes
-    // to the next waiting blob at the next window; a waiting one is never admitted.  *done:
-    // the bytes the windows gave it (0 for a waiting blob).
-    bool drop(uint32_t b, uint64_t* done) {
-        for (size_t k = 0; k < live_.size(); ++k)
-            if (live_[k].first == b) {
-                *done = live_[k].second;
-                live_.erase(live_.begin() + (long)k);
-                return true;
-            }
-        for (size_t k = q_; k < queue_.size(); ++k)
-            if (queue_[k] == b) {
-                *done = 0;
-                queue_.erase(queue_.begin() + (long)k);
-                return true;
-            }
-        return false;
-    }
-
-  private:
-    const uint64_t* L_;
-    uint64_t W_, cap_, align_;
-    std::vector<uint32_t> queue_;
-    size_t q_ = 0;
-    std::vector<std::pair<uint32_t, uint64_t>> live_;  // blob, bytes done
-    uint64_t max_live_ = 0;
-    uint64_t max_chunk_ = UINT64_MAX;
-};
+// The window schedule itself (WindowSched) is in window_math.hpp.
 
 // Live streams per window on device D: 7/8 of the largest stream count whose SHA-256 launch
 // still runs two (or eight) lanes a stream, a multiple of the two-pair workgroup's 64.
