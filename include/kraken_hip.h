@@ -549,6 +549,51 @@ int krk_ring_locations_u8_dev(const uint8_t* digests32_dev, uint64_t n, const kr
                               const uint8_t* healthy, int32_t max_replica,
                               uint8_t* locs_dev, uint8_t* counts_dev, void* stream);
 
+/* Ring ownership as bitsets: which of these blobs belong on this origin, and which change
+ * hands when the ring changes.  forceCleanupHandler -> maybeDelete
+ * (origin/blobserver/server.go:686-759) asks owns = stringset.FromSlice(hashRing.Locations(d))
+ * .Has(s.addr) of every cache file and deletes on expired || !owns; applyToReplicas
+ * (server.go:426-454) asks the same set question a blob.  Locations(d) depends on d only
+ * through its ShardID, so every such question is a 65,536-bit shard predicate: a mask of 1,024
+ * uint64 words, shard s = bit (s & 63) of word (s >> 6), built on the host from the tables
+ * krk_ring_owner_table returns (65,536 rows of `row` indices, counts[s] valid ones) and
+ * applied to n digests by krk_ring_select / krk_ring_select_dev: 1/8 byte a digest plus 8
+ * bytes a selected one, against the max(1, MaxReplica) + 1 bytes of krk_ring_locations_u8_dev.
+ * No device is needed for the masks or for krk_ring_select.
+ *
+ * krk_ring_mask_owns: mask[s] = node is one of Locations(s) (server.go:686-759 `owns`;
+ * "gained" / "lost" of a node between two memberships are owns_B & ~owns_A and its mirror).
+ * krk_ring_mask_moved: mask[s] = the owner SETS of s differ between membership A and B (sets,
+ * as maybeDelete and applyToReplicas use stringset, server.go:426-454: order is ignored).
+ * b_to_a[j] = the index in A of B's node j, -1 for a node A does not have; NULL = the same node
+ * list (only health or MaxReplica changed).  A NULL pointer, row == 0, a count above its row or
+ * a B owner outside [0, n_nodes_b) is KRK_EINVAL, refused before mask_out is touched. */
+int krk_ring_mask_owns(const int32_t* locs, const uint8_t* counts, uint32_t row, int32_t node,
+                       uint64_t* mask_out);
+int krk_ring_mask_moved(const int32_t* locs_a, const uint8_t* counts_a, uint32_t row_a,
+                        const int32_t* locs_b, const uint8_t* counts_b, uint32_t row_b,
+                        const int32_t* b_to_a, uint32_t n_nodes_b, uint64_t* mask_out);
+/* A mask applied to n raw 32-byte digests (server.go:686-759 over ListCacheFiles(), 426-454
+ * over a batch): sel(i) = (mask[ShardID(d_i)] ^ (invert != 0)) | or_bits[i].  or_bits
+ * (nullable) is n bits in the bitset layout -- the `expired` half of expired || !owns.
+ * bits_out: krk_bitfield_words(n) words, bit (i & 63) of word (i >> 6) = sel(i), the last
+ * word's tail bits 0, every word stored.  *count_out = the selected digests, always written
+ * (0 for n == 0).  idx_out (nullable; then idx_cap must be 0) receives the first
+ * min(count, idx_cap) selected i in ascending order -- the reference's `deleted` list is in
+ * listing order -- and nothing past them: count > idx_cap says the list is truncated. */
+int krk_ring_select(const uint8_t* digests32, uint64_t n, const uint64_t* mask, int invert,
+                    const uint64_t* or_bits, uint64_t* bits_out, uint64_t* idx_out, uint64_t idx_cap,
+                    uint64_t* count_out);
+/* The same for digests in device memory (any byte alignment), bit for bit (server.go:686-759,
+ * 426-454).  or_bits_dev, bits_out, idx_out and count_out are device memory or page-locked
+ * host memory (krk_host_alloc; as krk_ring_locations_dev the results are then on the host when
+ * the stream reaches the call's end) and 8-byte aligned: any other pointer is KRK_EINVAL before
+ * anything is launched.  mask_host is copied into the library's staging before the call
+ * returns; the call is asynchronous on `stream`.  KRK_ENODEV without a gfx950 device. */
+int krk_ring_select_dev(const uint8_t* digests32_dev, uint64_t n, const uint64_t* mask_host, int invert,
+                        const uint64_t* or_bits_dev, uint64_t* bits_out, uint64_t* idx_out,
+                        uint64_t idx_cap, uint64_t* count_out, void* stream);
+
 /* ------------------------------------------------ device memory helpers
  * For callers (benchmarks, cgo) that do not own a device allocator. */
 int krk_dev_alloc(uint64_t bytes, void** out);

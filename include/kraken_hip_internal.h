@@ -229,6 +229,10 @@ typedef struct krk_launch_rec {
 } krk_launch_rec;
 int krk_kernel_timeline(const char* kernel, krk_launch_rec* out, uint64_t cap, uint64_t* n);
 int krk_reset_kernel_stats(void);
+/* The shape of ring_select.hip as built (kernel name "ring_select"): the digests one workgroup
+ * takes, and the workgroup counts one scan tile holds -- the sizes at which
+ * krk_ring_select_dev's launches change shape, for the tests that pin its edges.  No device. */
+int krk_ring_select_geometry(uint64_t* digests_per_workgroup, uint64_t* scan_tile_workgroups);
 
 /* ------------------------------------------------------- SHA-256 plans
  * Lanes per stream (1, 2 or 8) the library uses for a batch of n_streams streams on

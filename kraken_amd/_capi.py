@@ -172,6 +172,11 @@ def _load() -> C.CDLL:
         "krk_ring_locations_dev": (i, [vp, C.c_uint64, nodesp, u8p, C.c_int32, vp, vp, vp]),
         "krk_ring_owner_table": (i, [nodesp, u8p, C.c_int32, i32p, u8p]),
         "krk_ring_locations_u8_dev": (i, [vp, C.c_uint64, nodesp, u8p, C.c_int32, vp, vp, vp]),
+        "krk_ring_mask_owns": (i, [i32p, u8p, C.c_uint32, C.c_int32, u64p]),
+        "krk_ring_mask_moved": (i, [i32p, u8p, C.c_uint32, i32p, u8p, C.c_uint32, i32p, C.c_uint32, u64p]),
+        "krk_ring_select": (i, [u8p, C.c_uint64, u64p, i, u64p, u64p, u64p, C.c_uint64, u64p]),
+        "krk_ring_select_dev": (i, [vp, C.c_uint64, u64p, i, vp, vp, vp, C.c_uint64, vp, vp]),
+        "krk_ring_select_geometry": (i, [u64p, u64p]),
         "krk_synth_fill_dev": (i, [vp, C.c_uint64, C.c_uint64, C.c_uint64, i, vp]),
         "krk_synth_fill_chunks_dev": (i, [C.POINTER(krk_chunk), C.c_uint64, i, vp]),
         "krk_dev_alloc": (i, [C.c_uint64, C.POINTER(vp)]),

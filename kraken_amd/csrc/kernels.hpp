@@ -255,6 +255,27 @@ hipError_t launch_pack_owner_rows(const int32_t* table_locs, const uint8_t* tabl
 hipError_t launch_shard_gather_packed(const uint8_t* digests32, uint64_t n, const uint32_t* packed,
                                       uint32_t row_out, uint8_t* locs, uint8_t* counts, hipStream_t s);
 
+// ---------------------------------------------------------------- ring select
+// A 65,536-bit shard predicate applied to n digests (ring_select.hip): bits[i >> 6] bit i & 63 =
+// (mask[ShardID(d_i)] ^ invert) | or_bits[i] (or_bits nullable; tail bits 0, every word stored),
+// *count_out = the selected digests (stored for n == 0 too), idx (nullable with idx_cap == 0) the
+// first min(count, idx_cap) selected i in ascending order.  mask: 2,048 words in device memory.
+// A workgroup takes kSelectW digests; the workgroup counts are scanned in tiles of kSelectT.
+constexpr uint32_t kSelectW = 1024;
+constexpr uint32_t kSelectT = 256;
+inline uint64_t ring_select_workgroups(uint64_t n) { return n / kSelectW + (n % kSelectW != 0); }
+inline uint64_t ring_select_tiles(uint64_t n) {
+    const uint64_t g = ring_select_workgroups(n);
+    return g / kSelectT + (g % kSelectT != 0);
+}
+// scratch: ring_select_scratch_bytes(n) of device memory, 8-byte aligned.
+inline uint64_t ring_select_scratch_bytes(uint64_t n) {
+    return 12 * ring_select_tiles(n) + 4 * ring_select_workgroups(n) + 8;
+}
+hipError_t launch_ring_select(const uint8_t* digests32, uint64_t n, const uint32_t* mask, int invert,
+                              const uint64_t* or_bits, uint64_t* bits, uint64_t* idx, uint64_t idx_cap,
+                              uint64_t* count_out, void* scratch, hipStream_t s);
+
 // ---------------------------------------------------------------- synthetic data
 // One synthetic chunk: bytes [offset, offset + n) of the blob whose stream seed is `seed`.
 struct SynthChunk {

@@ -1,6 +1,6 @@
 // runtime.hpp -- internal to libkraken_hip: device contexts, the stream-ordered
 // scratch cache, the CRC work builder and the SHA job runner shared by the C ABI
-// (runtime.cpp, batch_dev.cpp, info_hash_dev.cpp, crc_host.cpp, placement.cpp, windows.cpp) and the
+// (runtime.cpp, batch_dev.cpp, info_hash_dev.cpp, crc_host.cpp, placement.cpp, ring_select_abi.cpp, windows.cpp) and the
 // submission engine (engine.hpp, engine.cpp).  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -73,9 +73,10 @@ struct Event {
 };
 
 // ------------------------------------------------------------------ timing
-enum Kern { K_CRC, K_SHA, K_HRW, K_FILTER, K_GATHER, K_SYNTH, K_HOSTG, K_INFOHASH, K_BITFIELD, K_REPIECE, K_N };
+enum Kern { K_CRC, K_SHA, K_HRW, K_FILTER, K_GATHER, K_SYNTH, K_HOSTG, K_INFOHASH, K_BITFIELD, K_REPIECE, K_RSELECT, K_N };
 inline const char* kKernNames[K_N] = {"crc32_pieces", "sha256_multi", "hrw_order", "ring_filter",    "hrw_gather",
-                                      "synth_fill",   "host_gather",  "info_hash", "piece_bitfield", "piece_repiece"};
+                                      "synth_fill",   "host_gather",  "info_hash", "piece_bitfield", "piece_repiece",
+                                      "ring_select"};
 inline std::atomic<bool> g_timing{false};
 struct Pending {
     hipEvent_t a, b;
