@@ -31,6 +31,7 @@ extern "C" {
 #define KRK_ERANGE (-5)    /* output capacity too small */
 #define KRK_EHEX (-6)      /* invalid hex key (hrw.Score returns NaN, rendezvous.go:154-157) */
 #define KRK_EIO (-7)       /* file open/read failed (message has the path and errno text) */
+#define KRK_EFORMAT (-8)   /* a _torrentmeta document outside the canonical form (message says where) */
 
 /* ---------------------------------------------------------------- runtime */
 const char* krk_version(void);
@@ -261,6 +262,72 @@ int krk_repiece_batch(const krk_repiece_blob* blobs, uint64_t n, const uint32_t*
  * KRK_ENODEV without a gfx950 device. */
 int krk_repiece_batch_dev(const krk_repiece_blob* blobs_host, uint64_t n, const uint32_t* sums_dev,
                           uint32_t* out_dev, void* stream);
+
+/* ------------------------------------------------- _torrentmeta JSON (Serialize / Deserialize)
+ * MetaInfo.Serialize and DeserializeMetaInfo (core/metainfo.go:125-155): the sidecar's JSON,
+ * byte for byte what json.Marshal(&metaInfoJSON{info}) emits --
+ *   {"Info":{"PieceLength":I64,"PieceSums":ARR,"Name":"H64","Length":I64}}
+ *   I64 = -?(0|[1-9][0-9]{0,18}) in int64 range, never "-0"
+ *   ARR = null | [] | [U32(,U32)*]    U32 = 0|[1-9][0-9]{0,9}, <= 4294967295
+ *   H64 = 64 hex digits, either case
+ * with no whitespace and no trailing bytes: the canonical form.  The parser accepts exactly that
+ * form; anything else -- valid JSON that encoding/json would still unmarshal included -- is
+ * KRK_EFORMAT "metainfo json: not the canonical form at byte <i> of <n>" and belongs to the
+ * caller's general decoder.  `null` (a nil slice) and `[]` (an empty one) stay distinct in both
+ * directions.  The host forms need no device. */
+/* An upper bound of a document's size that depends on the sum count alone. */
+uint64_t krk_metainfo_json_bound(uint64_t n_sums);
+/* The document of (piece_length, sums[0, n_sums), name, length) to out[0, *len); sums_null != 0
+ * writes PieceSums as null (n_sums must be 0).  *len is the exact size whenever the arguments
+ * are valid: cap < *len is KRK_ERANGE with nothing written.  A name that is not 64 hex digits
+ * is KRK_EINVAL (its JSON escaping stays with the caller). */
+int krk_metainfo_serialize(int64_t piece_length, const uint32_t* sums, uint64_t n_sums, int sums_null,
+                           const char* name, uint64_t name_len, int64_t length, uint8_t* out, uint64_t cap,
+                           uint64_t* len);
+/* The four fields of a canonical document.  sums_cap >= (len + 1) / 2 always suffices; fewer
+ * than *n_sums is KRK_ERANGE with *n_sums set.  On KRK_EFORMAT nothing is promised about the
+ * outputs.  name_out receives the 64 name bytes as written (no terminator). */
+int krk_metainfo_parse(const uint8_t* data, uint64_t len, int64_t* piece_length, uint32_t* sums_out,
+                       uint64_t sums_cap, uint64_t* n_sums, int* sums_null, char name_out[64], int64_t* length);
+/* The envelope alone, O(1) work a document: the header from the front, the fixed-form trailer
+ * (,"Name":"...","Length":...}}) from the back, and [*arr_begin, *arr_end), the bytes strictly
+ * between '[' and ']' (empty for [] and for null), which are NOT looked at: they are
+ * krk_metainfo_parse_sums_batch_dev's part.  KRK_EFORMAT on any other envelope. */
+int krk_metainfo_json_envelope(const uint8_t* data, uint64_t len, int64_t* piece_length, uint64_t* arr_begin,
+                               uint64_t* arr_end, int* sums_null, char name_out[64], int64_t* length);
+/* The same codec on the device (metainfo_json.hip), asynchronous on `stream`; the descriptors
+ * are copied into the library's staging before a call returns.  Every device-side pointer is
+ * device memory or page-locked host memory (krk_host_alloc): any other pointer is KRK_EINVAL
+ * before anything is launched.  KRK_ENODEV without a gfx950 device; n == 0 is KRK_OK.
+ *
+ * Serialise: blob i's sums are sums_dev[sums_off, + n_sums); its document is stored at
+ * out + out_off, a slot of at least krk_metainfo_json_bound(n_sums) bytes the caller chose, and
+ * its exact size in out_len[i] (8-byte aligned).  Every byte of [out_off, out_off + out_len[i])
+ * is stored by the call and no byte outside it is touched; nothing is pre-zeroed.  Bytes equal
+ * to krk_metainfo_serialize's.  A name that is not 64 hex digits, or sums_null with n_sums != 0,
+ * is KRK_EINVAL. */
+typedef struct krk_metainfo_json_blob {
+    uint64_t sums_off, n_sums;             /* into sums_dev, in sums */
+    int64_t piece_length, length;
+    uint64_t out_off;                      /* into out, in bytes */
+    uint32_t sums_null, reserved;
+    char name[64];
+} krk_metainfo_json_blob;
+int krk_metainfo_serialize_batch_dev(const krk_metainfo_json_blob* blobs_host, uint64_t n, const uint32_t* sums_dev,
+                                     uint8_t* out, uint64_t* out_len, void* stream);
+/* Parse: span i is text_dev[text_off, + text_len), the bytes krk_metainfo_json_envelope found
+ * between the brackets (text_len == 0 for [] and for a null array, which bring no work);
+ * expect_n is the number of sums it must hold, krk_num_pieces(length, piece_length) of the
+ * envelope.  status[i] == 0 only if the span is canonical (U32(,U32)*, or empty) AND holds
+ * exactly expect_n numbers; then sums_out[sums_off, + expect_n) are its values.  With a nonzero
+ * status (bit 0: form, bit 1: count) those expect_n sums are unspecified; nothing outside them
+ * is written either way, and the caller pre-zeroes nothing. */
+typedef struct krk_metainfo_json_span {
+    uint64_t text_off, text_len;           /* into text_dev, in bytes */
+    uint64_t sums_off, expect_n;           /* into sums_out, in sums */
+} krk_metainfo_json_span;
+int krk_metainfo_parse_sums_batch_dev(const krk_metainfo_json_span* spans_host, uint64_t n, const uint8_t* text_dev,
+                                      uint32_t* sums_out, uint32_t* status, void* stream);
 
 /* ----------------------------------------------------- SHA-256 (Digester)
  * Replaces core.Digester (core/digester.go:28-72): crypto.SHA256 over the whole

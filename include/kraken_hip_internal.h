@@ -233,6 +233,11 @@ int krk_reset_kernel_stats(void);
  * takes, and the workgroup counts one scan tile holds -- the sizes at which
  * krk_ring_select_dev's launches change shape, for the tests that pin its edges.  No device. */
 int krk_ring_select_geometry(uint64_t* digests_per_workgroup, uint64_t* scan_tile_workgroups);
+/* The shape of metainfo_json.hip as built (kernel names "metainfo_serialize", "metainfo_parse"):
+ * the sums of one blob a serialise unit formats and the span bytes of one blob a parse unit
+ * reads -- the sizes at which the launches of krk_metainfo_serialize_batch_dev and
+ * krk_metainfo_parse_sums_batch_dev change shape, for the tests that pin their edges.  No device. */
+int krk_metainfo_json_geometry(uint64_t* serialize_unit_sums, uint64_t* parse_unit_bytes);
 
 /* ------------------------------------------------------- SHA-256 plans
  * Lanes per stream (1, 2 or 8) the library uses for a batch of n_streams streams on

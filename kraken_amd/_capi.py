@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("KRK_LIB_PATH") or os.path.join(_HERE, "lib", "libkrak
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "kraken_hip.h")
 INTERNAL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "kraken_hip_internal.h")
 
-KRK_OK, KRK_EINVAL, KRK_EHIP, KRK_ENOMEM, KRK_ENODEV, KRK_ERANGE, KRK_EHEX, KRK_EIO = 0, -1, -2, -3, -4, -5, -6, -7
+KRK_OK, KRK_EINVAL, KRK_EHIP, KRK_ENOMEM, KRK_ENODEV, KRK_ERANGE, KRK_EHEX, KRK_EIO, KRK_EFORMAT = 0, -1, -2, -3, -4, -5, -6, -7, -8
 KRK_PLACE_AUTO, KRK_PLACE_HOST, KRK_PLACE_GPU = 0, 1, 2
 KRK_OFFLOAD_AUTO = -1
 
@@ -39,6 +39,16 @@ class krk_file_blob(C.Structure):
 class krk_repiece_blob(C.Structure):
     _fields_ = [("length", C.c_int64), ("piece_length", C.c_int64), ("new_piece_length", C.c_int64),
                 ("sums_offset", C.c_uint64), ("out_offset", C.c_uint64)]
+
+
+class krk_metainfo_json_blob(C.Structure):
+    _fields_ = [("sums_off", C.c_uint64), ("n_sums", C.c_uint64), ("piece_length", C.c_int64), ("length", C.c_int64),
+                ("out_off", C.c_uint64), ("sums_null", C.c_uint32), ("reserved", C.c_uint32), ("name", C.c_char * 64)]
+
+
+class krk_metainfo_json_span(C.Structure):
+    _fields_ = [("text_off", C.c_uint64), ("text_len", C.c_uint64), ("sums_off", C.c_uint64),
+                ("expect_n", C.c_uint64)]
 
 
 class krk_chunk(C.Structure):
@@ -107,6 +117,14 @@ def _load() -> C.CDLL:
         "krk_repiece_sums": (i, [u32p, C.c_uint64, C.c_int64, C.c_int64, C.c_int64, u32p, C.c_uint64]),
         "krk_repiece_batch": (i, [C.POINTER(krk_repiece_blob), C.c_uint64, u32p, u32p]),
         "krk_repiece_batch_dev": (i, [C.POINTER(krk_repiece_blob), C.c_uint64, vp, vp, vp]),
+        "krk_metainfo_json_bound": (C.c_uint64, [C.c_uint64]),
+        "krk_metainfo_serialize": (i, [C.c_int64, vp, C.c_uint64, i, C.c_char_p, C.c_uint64, C.c_int64, vp,
+                                       C.c_uint64, u64p]),
+        "krk_metainfo_parse": (i, [vp, C.c_uint64, i64p, vp, C.c_uint64, u64p, C.POINTER(i), vp, i64p]),
+        "krk_metainfo_json_envelope": (i, [vp, C.c_uint64, i64p, u64p, u64p, C.POINTER(i), vp, i64p]),
+        "krk_metainfo_serialize_batch_dev": (i, [C.POINTER(krk_metainfo_json_blob), C.c_uint64, vp, vp, vp, vp]),
+        "krk_metainfo_parse_sums_batch_dev": (i, [C.POINTER(krk_metainfo_json_span), C.c_uint64, vp, vp, vp, vp]),
+        "krk_metainfo_json_geometry": (i, [u64p, u64p]),
         "krk_sha256_dev": (i, [C.POINTER(vp), u64p, C.c_uint64, vp, vp]),
         "krk_sha256_host": (i, [C.POINTER(vp), u64p, C.c_uint64, u8p]),
         "krk_sha256_dev_on_host": (i, [C.POINTER(vp), u64p, C.c_uint64, i, vp, u8p]),

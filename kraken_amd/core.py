@@ -21,7 +21,7 @@ import json
 
 import numpy as np
 
-from ._capi import KRK_EINVAL, KrakenError, check, krk_blob, lib
+from ._capi import KRK_EFORMAT, KRK_EINVAL, KrakenError, check, krk_blob, lib
 
 SHA256 = "sha256"
 DigestEmptyTar = "sha256:e3b0c44298fc1c149afbf4c8996fb92427ae41e4649b934ca495991b7852b855"
@@ -324,7 +324,22 @@ class MetaInfo:
         return MetaInfo(int(new_piece_length), sums, self._name, self._len, self._digest, ih)
 
     def Serialize(self) -> bytes:
-        """core/metainfo.go:131-134: json of {"Info": info} (field order as declared)."""
+        """core/metainfo.go:131-134: json of {"Info": info} (field order as declared), through
+        krk_metainfo_serialize; json.dumps below only for what the native call refuses (a name
+        that is not 64 hex digits, which needs JSON escaping) or cannot take (an integer outside
+        int64)."""
+        if -(1 << 63) <= self._pl < (1 << 63) and -(1 << 63) <= self._len < (1 << 63):
+            nb = self._name.encode()
+            s = np.ascontiguousarray(self.PieceSums(), dtype=np.uint32)
+            cap = int(lib.krk_metainfo_json_bound(s.size))
+            out = np.empty(cap, dtype=np.uint8)
+            n = C.c_uint64()
+            rc = lib.krk_metainfo_serialize(self._pl, s.ctypes.data if s.size else None, s.size, self._sums is None,
+                                            nb, len(nb), self._len, out.ctypes.data, cap, C.byref(n))
+            if rc == 0:
+                return out[:n.value].tobytes()
+            if rc != KRK_EINVAL:
+                check(rc)
         sums = None if self._sums is None else [int(x) for x in self._sums]
         obj = {"Info": {"PieceLength": self._pl, "PieceSums": sums, "Name": self._name,
                         "Length": self._len}}
@@ -406,7 +421,41 @@ def DeserializeMetaInfo(data: bytes) -> MetaInfo:
     """core/metainfo.go:136-155 with encoding/json's rules for metaInfoJSON: missing
     fields and a null Info take Go's zero values, so a truncated sidecar fails the way
     the reference does ("parse name: invalid sha256: ..."); type and range errors read
-    "json: cannot unmarshal <kind> into Go struct field info.<Field> of type <T>"."""
+    "json: cannot unmarshal <kind> into Go struct field info.<Field> of type <T>".
+
+    A document in the canonical form (what Serialize writes) is parsed by krk_metainfo_parse;
+    on KRK_EFORMAT -- anything else, valid or not -- the general decoder below runs unchanged,
+    so every encoding/json rule and error text comes from there."""
+    fields = _parse_canonical(data) if isinstance(data, (bytes, bytearray)) else None
+    if fields is None:
+        fields = _decode_general(data)
+    pl, arr, name, length = fields
+    ih = _info_hash(pl, arr if arr is not None else np.zeros(0, np.uint32), name, length)
+    try:
+        d = NewSHA256DigestFromHex(name)
+    except ValueError as e:
+        raise ValueError(f"parse name: {e}") from None
+    return MetaInfo(pl, arr, name, length, d, ih)
+
+
+def _parse_canonical(data):
+    """(piece length, sums or None, name, length) of a canonical document through
+    krk_metainfo_parse, None when the library refuses it as KRK_EFORMAT."""
+    raw = bytes(data)
+    sums = np.empty((len(raw) + 1) // 2 or 1, dtype=np.uint32)
+    pl, length, n, null = C.c_int64(), C.c_int64(), C.c_uint64(), C.c_int()
+    name = C.create_string_buffer(64)
+    rc = lib.krk_metainfo_parse(raw, len(raw), C.byref(pl), sums.ctypes.data, sums.size, C.byref(n), C.byref(null),
+                                name, C.byref(length))
+    if rc == KRK_EFORMAT:
+        return None
+    check(rc)
+    return pl.value, None if null.value else sums[:n.value].copy(), name.raw.decode(), length.value
+
+
+def _decode_general(data):
+    """encoding/json's Unmarshal into metaInfoJSON, any valid JSON: (piece length, sums or None,
+    name, length), or ValueError with Go's text."""
     try:
         j = json.loads(data, object_pairs_hook=_JObj, parse_float=_JNum)
         if j is None:
@@ -425,13 +474,7 @@ def DeserializeMetaInfo(data: bytes) -> MetaInfo:
     except (ValueError, TypeError) as e:
         raise ValueError(f"json: {e}") from None
     pl, sums, name, length = fields["PieceLength"], fields["PieceSums"], fields["Name"], fields["Length"]
-    arr = None if sums is None else np.asarray(sums, dtype=np.uint32)
-    ih = _info_hash(pl, arr if arr is not None else np.zeros(0, np.uint32), name, length)
-    try:
-        d = NewSHA256DigestFromHex(name)
-    except ValueError as e:
-        raise ValueError(f"parse name: {e}") from None
-    return MetaInfo(pl, arr, name, length, d, ih)
+    return pl, None if sums is None else np.asarray(sums, dtype=np.uint32), name, length
 
 
 def _as_bytes(p) -> np.ndarray:

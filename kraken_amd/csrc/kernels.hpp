@@ -201,6 +201,44 @@ static_assert(sizeof(RepieceBlob) == 48, "RepieceBlob layout");
 hipError_t launch_piece_repiece(const RepieceBlob* blobs, uint64_t n_blobs, uint64_t n_units, const uint32_t* x8pow,
                                 const uint32_t* sums, uint32_t* out, hipStream_t s);
 
+// ---------------------------------------------------------------- _torrentmeta JSON
+// One blob of a serialise batch (metainfo_json.hip): its sums are sums[first_sum, + n_sums), its
+// document goes to out + out_off.  first_unit ascends with the blob index (blob i's
+// mj::ser_units(n_sums) units follow blob i-1's) and blobs[0].first_unit == 0.
+struct alignas(16) MjSerBlob {
+    uint64_t first_sum;
+    uint64_t n_sums;
+    uint64_t out_off;
+    uint64_t first_unit;
+    int64_t piece_length;
+    int64_t length;
+    uint32_t sums_null;  // PieceSums is `null` (then n_sums == 0)
+    uint32_t pad[3];
+    uint8_t name[64];
+};
+static_assert(sizeof(MjSerBlob) == 128, "MjSerBlob layout");
+// scratch: mj_ser_scratch_bytes(n_units) of device memory, 8-byte aligned.  Every byte of every
+// document and every out_len[i] is stored.
+inline uint64_t mj_ser_scratch_bytes(uint64_t n_units) { return 8 * (n_units + 1) + 4 * n_units; }
+hipError_t launch_metainfo_serialize(const MjSerBlob* blobs, uint64_t n_blobs, uint64_t n_units, const uint32_t* sums,
+                                     uint8_t* out, uint64_t* out_len, void* scratch, hipStream_t s);
+// One blob of a parse batch: the span between its document's brackets is text[text_off,
+// + text_len), its expect_n sums go to sums_out[first_sum, + expect_n).  first_unit as above
+// (mj::parse_units(text_len) units a blob).
+struct alignas(16) MjParseBlob {
+    uint64_t text_off;
+    uint64_t text_len;
+    uint64_t first_sum;
+    uint64_t expect_n;
+    uint64_t first_unit;
+    uint64_t pad;
+};
+static_assert(sizeof(MjParseBlob) == 48, "MjParseBlob layout");
+inline uint64_t mj_parse_scratch_bytes(uint64_t n_units) { return 8 * (n_units + 1) + 8 * n_units; }
+hipError_t launch_metainfo_parse_sums(const MjParseBlob* blobs, uint64_t n_blobs, uint64_t n_units,
+                                      const uint8_t* text, uint32_t* sums_out, uint32_t* status, void* scratch,
+                                      hipStream_t s);
+
 // ---------------------------------------------------------------- host gather
 // One tile of a host -> device gather (gather.hip): n <= kGatherTile bytes from src (a
 // device-visible address of page-locked host memory: a hipHostMalloc'd or registered

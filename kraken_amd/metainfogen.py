@@ -25,7 +25,8 @@ import os
 import numpy as np
 
 from . import core
-from ._capi import KRK_EIO, check, krk_blob, krk_file_blob, krk_repiece_blob, lib
+from ._capi import (KRK_EIO, check, krk_blob, krk_file_blob, krk_metainfo_json_blob, krk_metainfo_json_span,
+                    krk_repiece_blob, lib)
 
 
 class pieceLengthConfig:
@@ -90,8 +91,12 @@ class DirCAS:
             return f.read()
 
     def SetCacheFileMetadata(self, hex_: str, mi: core.MetaInfo) -> bool:
+        return self.SetCacheFileMetadataBytes(hex_, mi.Serialize())
+
+    def SetCacheFileMetadataBytes(self, hex_: str, b: bytes) -> bool:
+        """SetCacheFileMetadata for a sidecar that is serialised already (the device codec's
+        documents): the same compare-then-write, the same `changed` return."""
         p = os.path.join(self._dir(hex_), "_torrentmeta")
-        b = mi.Serialize()
         if os.path.exists(p) and open(p, "rb").read() == b:
             return False
         with open(p, "wb") as f:
@@ -126,6 +131,81 @@ class DirCAS:
         with open(os.path.join(self._dir(d.Hex()), "data"), "wb") as f:
             f.write(data)
         return d
+
+
+def repiece_sidecars_dev(entries) -> dict:
+    """{name: the new sidecar's bytes} for entries' [(name, blob size, target piece length, stored
+    sidecar bytes)]: sidecar bytes in, sidecar bytes out, no per-sum host work.  Per stored sidecar
+    the host reads the envelope (krk_metainfo_json_envelope, O(1)) and makes
+    Generator._stored_metainfo's no-read checks on it -- the Name is the blob's, the Length its
+    size, the piece length positive -- and RepieceAll's: the piece length divides the target and is
+    not the target.  Then one upload of the spans between the brackets, and on one stream
+    krk_metainfo_parse_sums_batch_dev -> krk_repiece_batch_dev -> krk_info_hash_batch_dev ->
+    krk_metainfo_serialize_batch_dev, one copy back of [documents][lengths][statuses].  (The
+    InfoHashes stay on the device: the sidecar does not hold them.)  A blob whose envelope is
+    refused, whose span is not canonical or does not hold the blob's number of sums (a nonzero
+    device status) or that fails a check is not in the result: it belongs to the general path."""
+    from . import device as D
+    cand, texts = [], []
+    pl, ln, a0, a1, null = C.c_int64(), C.c_int64(), C.c_uint64(), C.c_uint64(), C.c_int()
+    nm = C.create_string_buffer(64)
+    for name, size, target, raw in entries:
+        if lib.krk_metainfo_json_envelope(raw, len(raw), C.byref(pl), C.byref(a0), C.byref(a1), C.byref(null), nm,
+                                          C.byref(ln)) != 0:
+            continue
+        p = pl.value
+        if nm.raw.decode() != name or ln.value != size or p <= 0 or target <= 0 or target == p or target % p:
+            continue
+        cand.append((name, size, p, target))
+        texts.append(raw[a0.value:a1.value])
+    n = len(cand)
+    if not n:
+        return {}
+    spans = (krk_metainfo_json_span * n)()
+    rp = (krk_repiece_blob * n)()
+    ser = (krk_metainfo_json_blob * n)()
+    t = a = b = o = 0
+    for i, ((name, size, p, target), text) in enumerate(zip(cand, texts)):
+        n_old, n_new = int(lib.krk_num_pieces(size, p)), int(lib.krk_num_pieces(size, target))
+        spans[i] = krk_metainfo_json_span(t, len(text), a, n_old)
+        rp[i] = krk_repiece_blob(size, p, target, a, b)
+        ser[i] = krk_metainfo_json_blob(b, n_new, target, size, o, n_new == 0, 0, name.encode())
+        t, a, b = t + len(text), a + n_old, b + n_new
+        o += int(lib.krk_metainfo_json_bound(n_new))
+    # one device buffer: [spans' text][stored sums][new sums][InfoHashes] then the part that
+    # comes back, [documents][lengths][statuses]
+    up = lambda x, to: (x + to - 1) // to * to
+    at_old = up(t, 4)
+    at_new = at_old + 4 * a
+    at_ih = at_new + 4 * b
+    at_doc = up(at_ih + 20 * n, 8)
+    at_len = up(at_doc + o, 8)
+    at_st = at_len + 8 * n
+    end = at_st + 4 * n
+    dev = D.DeviceBuffer(end)
+    back = D.PinnedArray((end - at_doc,), np.uint8)
+    try:
+        dev.from_host(np.frombuffer(b"".join(texts), dtype=np.uint8))
+        check(lib.krk_metainfo_parse_sums_batch_dev(spans, n, dev.ptr, dev.ptr + at_old, dev.ptr + at_st, None))
+        check(lib.krk_repiece_batch_dev(rp, n, dev.ptr + at_old, dev.ptr + at_new, None))
+        buf, noff = D.pack_names([c[0] for c in cand])
+        i64p, u64p = C.POINTER(C.c_int64), C.POINTER(C.c_uint64)
+        col = lambda v, dt: np.ascontiguousarray(v, dtype=dt)
+        pl_, ln_ = col([c[3] for c in cand], np.int64), col([c[1] for c in cand], np.int64)
+        so_, ns_ = col([x.sums_off for x in ser], np.uint64), col([x.n_sums for x in ser], np.uint64)
+        check(lib.krk_info_hash_batch_dev(pl_.ctypes.data_as(i64p), dev.ptr + at_new, so_.ctypes.data_as(u64p),
+                                          ns_.ctypes.data_as(u64p), buf or None, noff.ctypes.data_as(u64p),
+                                          ln_.ctypes.data_as(i64p), n, dev.ptr + at_ih, None))
+        check(lib.krk_metainfo_serialize_batch_dev(ser, n, dev.ptr + at_new, dev.ptr + at_doc, dev.ptr + at_len,
+                                                   None))
+        back.fill_from_async(dev, None, at_doc)
+        check(lib.krk_stream_sync(None))
+        lens = back.a[at_len - at_doc:at_st - at_doc].view(np.uint64)
+        status = back.a[at_st - at_doc:].view(np.uint32)
+        return {c[0]: back.a[int(x.out_off):int(x.out_off) + int(lens[i])].tobytes()
+                for i, (c, x) in enumerate(zip(cand, ser)) if status[i] == 0}
+    finally:
+        dev.free()
 
 
 class Generator:
@@ -223,19 +303,28 @@ class Generator:
         reading only the blobs whose stored sums cannot serve.  Per blob, with its usable stored
         sidecar (_stored_metainfo): the target equals the stored piece length: ``unchanged``; the
         stored one divides it: ``repieced`` from the stored sums -- all of them in ONE
-        krk_repiece_batch call (placement "host"), or (placement "gpu") ONE krk_repiece_batch_dev
-        then krk_info_hash_batch_dev on the same stream and one copy back; everything else, a
+        krk_repiece_batch call (placement "host"), or (placement "gpu") one device chain from the
+        stored sidecars' bytes to the new sidecars' bytes (_repiece_chain_dev); everything else, a
         missing or unusable sidecar included: ``reread`` through GenerateBatch in batches of
         ~batch_bytes.  Returns {"blobs", "unchanged", "repieced", "reread", "changed" (sidecars
         whose bytes changed), "bytes_not_read" (the sizes of the unchanged and repieced blobs)}."""
         if placement not in ("host", "gpu"):
             raise ValueError(f"unknown placement {placement!r}")
         names = self.cas.ListNames()
-        unchanged = changed = bytes_not_read = 0
+        sizes = [self.cas.GetCacheFileStat(name).st_size for name in names]
+        targets = [self.pieceLengthConfig.get(size) for size in sizes]
+        docs = self._repiece_chain_dev(names, sizes, targets) if placement == "gpu" else {}
+        unchanged = changed = bytes_not_read = repieced = 0
         todo, reread = [], []
-        for name in names:
-            size = self.cas.GetCacheFileStat(name).st_size
-            target = self.pieceLengthConfig.get(size)
+        for name, size, target in zip(names, sizes, targets):
+            if name in docs:
+                repieced += 1
+                bytes_not_read += size
+                try:
+                    changed += bool(self.cas.SetCacheFileMetadataBytes(name, docs[name]))
+                except OSError as e:
+                    raise IOError(f"set metainfo: {e}") from None
+                continue
             mi = self._stored_metainfo(name, size)
             if mi is not None and target == mi.PieceLength():
                 unchanged += 1
@@ -246,7 +335,7 @@ class Generator:
             else:
                 reread.append((name, size))
         if todo:
-            for (name, mi, target), (sums, ih) in zip(todo, self._repiece_batch(todo, placement)):
+            for (name, mi, target), (sums, ih) in zip(todo, self._repiece_batch(todo)):
                 new = core.MetaInfo(target, sums, name, mi.Length(), mi.Digest(), ih)
                 try:
                     changed += bool(self.cas.SetCacheFileMetadata(name, new))
@@ -260,11 +349,12 @@ class Generator:
                 self.GenerateBatch(batch)
                 changed += self._last_changed
                 batch, size = [], 0
-        return {"blobs": len(names), "unchanged": unchanged, "repieced": len(todo), "reread": len(reread),
+        return {"blobs": len(names), "unchanged": unchanged, "repieced": repieced + len(todo), "reread": len(reread),
                 "changed": changed, "bytes_not_read": bytes_not_read}
 
-    def _repiece_batch(self, todo, placement: str):
-        """[(new sums or None, InfoHash)] of todo's [(name, stored MetaInfo, new piece length)]."""
+    def _repiece_batch(self, todo):
+        """[(new sums or None, InfoHash)] of todo's [(name, stored MetaInfo, new piece length)]:
+        ONE krk_repiece_batch and one krk_info_hash_batch, on the host."""
         n = len(todo)
         arr = (krk_repiece_blob * n)()
         a = b = 0
@@ -277,32 +367,21 @@ class Generator:
         counts = [int(lib.krk_num_pieces(mi.Length(), target)) for _, mi, target in todo]
         pls, lens, hexes = [t for *_, t in todo], [mi.Length() for _, mi, _ in todo], [name for name, *_ in todo]
         u32p = C.POINTER(C.c_uint32)
-        if placement == "host":
-            out = np.zeros(max(b, 1), dtype=np.uint32)
-            check(lib.krk_repiece_batch(arr, n, old.ctypes.data_as(u32p) if old.size else None, out.ctypes.data_as(u32p)))
-            ihs = core._info_hash_batch(pls, out, offs, counts, hexes, lens)
-        else:
-            from . import device as D
-            d_old = D.DeviceBuffer(4 * max(a, 1))
-            d_old.from_host(old)
-            ih_at = (4 * b + 15) & ~15  # [new sums][InfoHashes]: one buffer, one copy back
-            d_out = D.DeviceBuffer(ih_at + 20 * n)
-            back = D.PinnedArray((ih_at + 20 * n,), np.uint8)
-            check(lib.krk_repiece_batch_dev(arr, n, d_old.ptr, d_out.ptr, None))
-            buf, noff = D.pack_names(hexes)
-            i64p, u64p = C.POINTER(C.c_int64), C.POINTER(C.c_uint64)
-            col = lambda v, dt: np.ascontiguousarray(v, dtype=dt)
-            pl_, so_, ns_, ln_ = col(pls, np.int64), col(offs, np.uint64), col(counts, np.uint64), col(lens, np.int64)
-            check(lib.krk_info_hash_batch_dev(pl_.ctypes.data_as(i64p), d_out.ptr, so_.ctypes.data_as(u64p),
-                                              ns_.ctypes.data_as(u64p), buf or None, noff.ctypes.data_as(u64p),
-                                              ln_.ctypes.data_as(i64p), n, d_out.ptr + ih_at, None))
-            back.fill_from_async(d_out, None)
-            check(lib.krk_stream_sync(None))
-            out = back.a[:4 * b].view(np.uint32).copy()
-            ihs = [core.InfoHash(bytes(back.a[ih_at + 20 * i:ih_at + 20 * i + 20])) for i in range(n)]
-            d_old.free()
-            d_out.free()
+        out = np.zeros(max(b, 1), dtype=np.uint32)
+        check(lib.krk_repiece_batch(arr, n, old.ctypes.data_as(u32p) if old.size else None, out.ctypes.data_as(u32p)))
+        ihs = core._info_hash_batch(pls, out, offs, counts, hexes, lens)
         return [(out[o:o + c].copy() if c else None, ih) for o, c, ih in zip(offs, counts, ihs)]
+
+    def _repiece_chain_dev(self, names, sizes, targets) -> dict:
+        """{name: the new sidecar's bytes} of the blobs repiece_sidecars_dev re-pieces from the
+        stored sidecars' bytes; a blob without a readable sidecar is not among them."""
+        entries = []
+        for name, size, target in zip(names, sizes, targets):
+            try:
+                entries.append((name, size, target, self.cas.GetCacheFileMetadata(name)))
+            except OSError:
+                continue
+        return repiece_sidecars_dev(entries)
 
     def VerifyAll(self, batch_bytes: int = 8 << 30, check_digest: bool = True) -> dict:
         """The read-only counterpart of RegenerateAll: every cached blob against the
