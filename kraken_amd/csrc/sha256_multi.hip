@@ -21,6 +21,7 @@
 
 #include <atomic>
 #include <mutex>
+#include <type_traits>
 
 #include "../../include/kraken_hip_internal.h"
 #include "kernels.hpp"
@@ -476,14 +477,16 @@ struct TwoLaneConst {
 // each quad rotates once and its state is never read.  8 streams a wave.  The first
 // DPP xor reads t1 three instructions after it is written (two wait states needed),
 // the cross add reads a register written a round earlier.
-#define KRK_SHA8_ROUND(X0, X1, X2, NX, WN)                                                   \
+#define KRK_SHA8_ROUND(X0, X1, X2, NX, WN) KRK_SHA8_ROUND_(X0, X1, X2, NX, "%[" #WN "]")
+// W: the W operand as text, a named operand or (block8p) a pinned register
+#define KRK_SHA8_ROUND_(X0, X1, X2, NX, W)                                                   \
     "v_alignbit_b32 %[t1], %[" #X0 "], %[" #X0 "], %[r1]\n\t"                               \
     "v_bitop3_b32 %[k], %[" #X0 "], %[" #X1 "], %[ma] bitop3:0x2d\n\t"                      \
     "v_bitop3_b32 %[k], %[k], %[" #X2 "], %[" #X1 "] bitop3:0xca\n\t"                       \
     "v_xor_b32_dpp %[t2], %[t1], %[t1] quad_perm:[1,2,0,3] row_mask:0xf bank_mask:0xf\n\t"  \
     "v_xor_b32_dpp %[t2], %[t1], %[t2] quad_perm:[2,0,1,3] row_mask:0xf bank_mask:0xf\n\t"  \
     "v_add_u32_dpp %[p], %[" #X1 "], %[z] row_ror:8 row_mask:0xf bank_mask:0xf\n\t"          \
-    "v_xad_u32 %[z], %[" #X2 "], %[ma], %[" #WN "]\n\t"                                     \
+    "v_xad_u32 %[z], %[" #X2 "], %[ma], " W "\n\t"                                          \
     "v_add3_u32 %[" #NX "], %[t2], %[k], %[p]\n\t"
 #define KRK_SHA8_OPERANDS                                                                    \
     : [t1] "=&v"(t1), [t2] "=&v"(t2), [k] "=&v"(kk), [p] "=&v"(p), [z] "+v"(z), [R0] "+v"(R0), \
@@ -514,44 +517,52 @@ constexpr int kAhead = KRK_SHA_AHEAD;
 #define KRK_SHA8_UNROLL 4  // eight-lane consumer: blocks per loop iteration
 static_assert(kAhead >= 2 && kAhead <= 8, "read-ahead distance");
 
-// Rounds n = 4j + 2 .. 4j + 5 of an eight-lane block (block8p), the register roles of
-// instruction-rounds 2 .. 5: W operands are W[n + 1] for the z of the next round.
-__device__ __forceinline__ void sha8_quad2(uint32_t& R0, uint32_t& R1, uint32_t& R2, uint32_t& R3, uint32_t& z,
-                                           const TwoLaneConst& c, uint32_t w1, uint32_t w2, uint32_t w3,
-                                           uint32_t w4) {
-    uint32_t t1, t2, kk, p;
-    asm volatile(KRK_SHA8_ROUND(R2, R1, R0, R3, w1) KRK_SHA8_ROUND(R3, R2, R1, R0, w2)
-                 KRK_SHA8_ROUND(R0, R3, R2, R1, w3) KRK_SHA8_ROUND(R1, R0, R3, R2, w4)
-                 KRK_SHA8_OPERANDS
-                 : KRK_SHA8_CONSTS, [w1] "v"(w1), [w2] "v"(w2), [w3] "v"(w3), [w4] "v"(w4));
-}
-
-// W read groups of the eight-lane consumer: three quads read between 12-round asm blocks, four quads ahead (a group's last block
-// needs quad j + 3, read one group earlier), so ONE s_waitcnt precedes every 12 rounds;
-// 1 = one read and one wait per 4 rounds (round 2's first form).  C2-shaped A/B on one
-// box (profiles/r02/sha8_read_groups.jsonl): 56.2 MB/s a stream with one read a group,
-// 57.2 with pairs, 58.7 with threes, 58.3 with fives (two asm statements a group); the
-// threes' reads issued mid-way through the previous group (two six-round statements)
-// instead of right before its wait: 59.1 vs 59.2 (profiles/r02/sha8_read_split.jsonl).
-constexpr int kAhead8 = 4;
-// Twelve eight-lane rounds, n = 4j + 2 .. 4j + 13: W quads a = j, b = j + 1, d = j + 2,
-// e = j + 3 (each block of four takes its first quad's last word and the next quad's
-// first three).
-__device__ __forceinline__ void sha8_dodec2(uint32_t& R0, uint32_t& R1, uint32_t& R2, uint32_t& R3, uint32_t& z,
-                                            const TwoLaneConst& c, const u32x4& a, const u32x4& b, const u32x4& d,
-                                            const u32x4& e) {
-    uint32_t t1, t2, kk, p;
-    asm volatile(KRK_SHA8_ROUND(R2, R1, R0, R3, w1) KRK_SHA8_ROUND(R3, R2, R1, R0, w2)
-                 KRK_SHA8_ROUND(R0, R3, R2, R1, w3) KRK_SHA8_ROUND(R1, R0, R3, R2, w4)
-                 KRK_SHA8_ROUND(R2, R1, R0, R3, w5) KRK_SHA8_ROUND(R3, R2, R1, R0, w6)
-                 KRK_SHA8_ROUND(R0, R3, R2, R1, w7) KRK_SHA8_ROUND(R1, R0, R3, R2, w8)
-                 KRK_SHA8_ROUND(R2, R1, R0, R3, w9) KRK_SHA8_ROUND(R3, R2, R1, R0, w10)
-                 KRK_SHA8_ROUND(R0, R3, R2, R1, w11) KRK_SHA8_ROUND(R1, R0, R3, R2, w12)
-                 KRK_SHA8_OPERANDS
-                 : KRK_SHA8_CONSTS, [w1] "v"(a[3]), [w2] "v"(b[0]), [w3] "v"(b[1]), [w4] "v"(b[2]),
-                   [w5] "v"(b[3]), [w6] "v"(d[0]), [w7] "v"(d[1]), [w8] "v"(d[2]), [w9] "v"(d[3]),
-                   [w10] "v"(e[0]), [w11] "v"(e[1]), [w12] "v"(e[2]));
-}
+// W delivery of the eight-lane consumer: the ds_read_b128 and the s_waitcnt of a block
+// sit INSIDE the block's one asm statement (block8p), so the compiler places none of its
+// own.  W lives in sixteen pinned quads v[64:127], word m of the block in v(64 + m):
+// the rounds name the registers, the quads that cross a statement (the first kHeld8 of a
+// block) are operands tied to their registers, the rest clobbers.  What costs is every
+// break of the round stream, not the wait or the read as such (same-box C2 steps,
+// profiles/r07/sha8_w_delivery_ab.jsonl): the compiler's six groups a block 1,775 ms, the
+// same sixteen reads issued one by one between rounds with two waits 1,807 ms, two bursts
+// 1,764 ms.  So a block breaks twice, each time one s_waitcnt lgkmcnt(0) and eight reads,
+// after the first round of quad-time 0 and of quad-time 8 (that round takes the last
+// word of the quad whose registers the burst's last read refills):
+//   burst A: waits for the previous burst B (quads 1 .. 8), reads quads 9 .. 15 and the
+//     NEXT block's quad 0 into quad 0's registers (rounds 63 .. 65 and the next block's
+//     first round take their W from it);
+//   burst B: waits for burst A, reads the next block's quads 1 .. 8.
+// Each wait comes 32 rounds (~1,200 cycles) after the reads it waits for, so it never
+// stalls on a read still on its way, and being a full wait it also covers a scalar load,
+// which lgkmcnt counts too (the loop has none).  Every W quad is read at least four quads
+// before its first use, as before.
+// INVARIANT the compiler is not told: when a block's statement ends, burst B's reads are
+// still landing in the tied operands k[1] .. k[8] (v[68:99]); only the next statement's
+// wait A, or the kernel's wait after the loop, makes them valid.  This holds as long as the
+// compiler emits nothing that reads or moves v64 .. v99 between two block statements: no
+// copy, no spill, no use of kq in C++.  Tying every kq[] to the same registers in every
+// statement leaves it no reason to, and the disassembly shows none, but it is a property
+// of the generated code: after a compiler change, or any edit of the loop in
+// sha256_w8_kernel, check in the disassembly (tools/sha_isa.py --lanes 8 finds the loop)
+// that between the block statements only SALU bookkeeping and the address adds remain.
+constexpr int kHeld8 = 9;
+#define KRK_SHA8_RD(Q0, Q1, BASE, OFF, Q) \
+    "ds_read_b128 v[" #Q0 ":" #Q1 "], %[" #BASE "] offset:%[" #OFF "]+" #Q "*1024\n\t"
+// A quad-time: rounds n = 4t + 2 .. 4t + 5, W words 4t + 3 .. 4t + 6; B is a burst (or
+// nothing) issued after its first round, which takes the last word of quad t.
+#define KRK_SHA8_QT(W1, W2, W3, W4, B)                                                \
+    KRK_SHA8_ROUND_(R2, R1, R0, R3, #W1) B KRK_SHA8_ROUND_(R3, R2, R1, R0, #W2)      \
+    KRK_SHA8_ROUND_(R0, R3, R2, R1, #W3) KRK_SHA8_ROUND_(R1, R0, R3, R2, #W4)
+#define KRK_SHA8_BURST_A                                                                          \
+    "s_waitcnt lgkmcnt(0)\n\t"                                                                    \
+    KRK_SHA8_RD(100, 103, cb, co, 9) KRK_SHA8_RD(104, 107, cb, co, 10) KRK_SHA8_RD(108, 111, cb, co, 11) \
+    KRK_SHA8_RD(112, 115, cb, co, 12) KRK_SHA8_RD(116, 119, cb, co, 13) KRK_SHA8_RD(120, 123, cb, co, 14) \
+    KRK_SHA8_RD(124, 127, cb, co, 15) KRK_SHA8_RD(64, 67, nb, no, 0)
+#define KRK_SHA8_BURST_B                                                                          \
+    "s_waitcnt lgkmcnt(0)\n\t"                                                                    \
+    KRK_SHA8_RD(68, 71, nb, no, 1) KRK_SHA8_RD(72, 75, nb, no, 2) KRK_SHA8_RD(76, 79, nb, no, 3)   \
+    KRK_SHA8_RD(80, 83, nb, no, 4) KRK_SHA8_RD(84, 87, nb, no, 5) KRK_SHA8_RD(88, 91, nb, no, 6)   \
+    KRK_SHA8_RD(92, 95, nb, no, 7) KRK_SHA8_RD(96, 99, nb, no, 8)
 
 // Eight lanes a stream, blocks pipelined: the A quad runs rounds 62, 63 of block i
 // while the E quad already runs rounds 0, 1 of block i + 1, so a block costs 64
@@ -574,90 +585,86 @@ __device__ __forceinline__ void sha8_dodec2(uint32_t& R0, uint32_t& R1, uint32_t
 //   F3 (A finished block i): A's round 0 of block i + 1 takes -d from z formed on raw
 //      a61: z -= hA[1]; R += hA; hA <- R where i < the block count.
 // A finished stream's lanes keep computing on garbage; their hE / hA stay frozen.
+// cur / nxt: LDS byte addresses (a VGPR and a constant each) of quad 0 of this block's
+// and the next block's column; k: the first kHeld8 W quads, this block's on entry and
+// the next block's (in flight) on return.
+template <uint32_t kCurOff, uint32_t kNxtOff>
 __device__ __forceinline__ void block8p(uint32_t& R0, uint32_t& R1, uint32_t& R2, uint32_t& R3, uint32_t& z,
                                         uint32_t hE[4], uint32_t hA[4], uint32_t mineE, uint32_t mineA,
-                                        uint32_t i, const uint32_t* lds, uint32_t cbase, uint32_t nbase,
-                                        const TwoLaneConst& c, u32x4 k[kAhead8]) {
-    constexpr int kRS = kAhead8 + 1;
-    u32x4 wq[kRS];
-#pragma unroll
-    for (int j = 0; j < kAhead8; ++j) wq[j] = k[j];
-    // Rounds n = 2 .. 61: 5 asm blocks of twelve rounds,
-    // the next three W quads read before each (four quads ahead), so one s_waitcnt per
-    // twelve rounds.  Otherwise 15 asm blocks of four, n = 4j + 2 .. 4j + 5 (W: quad j's
-    // last word, quad j + 1's first three), each W read between two blocks -- two rounds
-    // into a W quad (issued right before a W quad's rounds a read cost ~16 cycles of the
-    // wave's stream, two rounds in ~8, tools/micro/sha8lds.hip); the read + its wait
-    // between two asm blocks are the two wait states the hazard recognizer would pad.
-    constexpr int RS = kAhead8 + 3;
-    u32x4 wr[RS];
-#pragma unroll
-    for (int j = 0; j < kAhead8; ++j) wr[j] = wq[j];
-    auto rd = [&](int q) {  // W quad q of this block (q < 16) or q - 16 of the next block
-        if (q < 16) wr[q % RS] = *reinterpret_cast<const u32x4*>(lds + cbase + 256 * q);
-        else k[q - 16] = *reinterpret_cast<const u32x4*>(lds + nbase + 256 * (q - 16));
-    };
-#pragma unroll
-    for (int j = 0; j < 15; j += 3) {
-        rd(j + kAhead8);
-        rd(j + kAhead8 + 1);
-        rd(j + kAhead8 + 2);
-        sha8_dodec2(R0, R1, R2, R3, z, c, wr[j % RS], wr[(j + 1) % RS], wr[(j + 2) % RS], wr[(j + 3) % RS]);
-    }
-    wq[15 % kRS] = wr[15 % RS];
-    k[kAhead8 - 1] = *reinterpret_cast<const u32x4*>(lds + nbase + 256 * (kAhead8 - 1));
-    {
-        uint32_t t1, t2, kk, p;  // n = 62, 63
-        asm volatile(KRK_SHA8_ROUND(R2, R1, R0, R3, w3)
-                     KRK_SHA8_ROUND(R3, R2, R1, R0, w4)
-                     KRK_SHA8_OPERANDS
-                     : KRK_SHA8_CONSTS, [w3] "v"(wq[15 % kRS][3]), [w4] "v"(k[0][0]));
-    }
-    {
-        // F1, n = 64, F2, n = 65, F3.  The cross terms go through one DPP each: every
-        // lane forms hA - hE of its own (E lanes: -hE, A lanes: hA) and reads its
-        // partner's, so E picks up the A half's H2 / H3 and A gives back E's H4 / H5.
-        // (v_subrev_u32_dpp swizzles its second operand on gfx950, tools/micro/dppsem.hip,
-        // so it is not used.)  Every VGPR a DPP instruction reads is written at least two
-        // instructions earlier.
-        uint32_t t1, t2, kk, p, cc, dd, c2;
-        asm volatile("v_sub_u32_e32 %[cc], %[a0], %[e0]\n\t"   // own hA0 - hE0
-                     "v_sub_u32_e32 %[dd], %[a1], %[e1]\n\t"   // own hA1 - hE1
-                     "v_add_u32_e32 %[R0], %[e0], %[R0]\n\t"
-                     "v_add_u32_e32 %[R3], %[e1], %[R3]\n\t"
-                     "v_mov_b32_dpp %[c2], %[cc] row_ror:8 row_mask:0xf bank_mask:0xf\n\t"  // E: H2 of A, A: -H4
-                     "v_add_u32_dpp %[z], %[dd], %[z] row_ror:8 row_mask:0xf bank_mask:0xf\n\t"  // E: +H3 of A, A: -H5
-                     "v_add_u32_e32 %[R2], %[e2], %[R2]\n\t"
-                     "v_add_u32_e32 %[R1], %[e3], %[R1]\n\t"
-                     "v_add_u32_e32 %[z], %[e3], %[z]\n\t"
-                     "v_cmp_lt_u32_e32 vcc, %[i], %[mineE]\n\t"
-                     "v_cndmask_b32_e32 %[e0], %[e0], %[R0], vcc\n\t"
-                     "v_cndmask_b32_e32 %[e1], %[e1], %[R3], vcc\n\t"
-                     "v_cndmask_b32_e32 %[e2], %[e2], %[R2], vcc\n\t"
-                     "v_cndmask_b32_e32 %[e3], %[e3], %[R1], vcc\n\t"
-                     KRK_SHA8_ROUND(R0, R3, R2, R1, w1)
-                     "v_add_u32_e32 %[z], %[c2], %[z]\n\t"
-                     KRK_SHA8_ROUND(R1, R0, R3, R2, w2)
-                     "v_sub_u32_e32 %[z], %[z], %[a1]\n\t"
-                     "v_add_u32_e32 %[R0], %[a0], %[R0]\n\t"
-                     "v_add_u32_e32 %[R3], %[a1], %[R3]\n\t"
-                     "v_add_u32_e32 %[R2], %[a2], %[R2]\n\t"
-                     "v_add_u32_e32 %[R1], %[a3], %[R1]\n\t"
-                     "v_cmp_lt_u32_e32 vcc, %[i], %[mineA]\n\t"
-                     "v_cndmask_b32_e32 %[a0], %[a0], %[R0], vcc\n\t"
-                     "v_cndmask_b32_e32 %[a1], %[a1], %[R3], vcc\n\t"
-                     "v_cndmask_b32_e32 %[a2], %[a2], %[R2], vcc\n\t"
-                     "v_cndmask_b32_e32 %[a3], %[a3], %[R1], vcc\n\t"
-                     : [t1] "=&v"(t1), [t2] "=&v"(t2), [k] "=&v"(kk), [p] "=&v"(p), [cc] "=&v"(cc), [dd] "=&v"(dd),
-                       [c2] "=&v"(c2), [z] "+v"(z),
-                       [R0] "+v"(R0), [R1] "+v"(R1), [R2] "+v"(R2), [R3] "+v"(R3), [e0] "+v"(hE[0]),
-                       [e1] "+v"(hE[1]), [e2] "+v"(hE[2]), [e3] "+v"(hE[3]), [a0] "+v"(hA[0]), [a1] "+v"(hA[1]),
-                       [a2] "+v"(hA[2]), [a3] "+v"(hA[3])
-                     : KRK_SHA8_CONSTS, [w1] "v"(k[0][1]), [w2] "v"(k[0][2]), [i] "s"(i), [mineE] "v"(mineE),
-                       [mineA] "v"(mineA)
-                     : "vcc");
-    }
+                                        uint32_t i, uint32_t cur, uint32_t nxt, const TwoLaneConst& c,
+                                        u32x4 k[kHeld8]) {
+    // The cross terms of F1 .. F3 go through one DPP each: every lane forms hA - hE of
+    // its own (E lanes: -hE, A lanes: hA) and reads its partner's, so E picks up the A
+    // half's H2 / H3 and A gives back E's H4 / H5.  (v_subrev_u32_dpp swizzles its second
+    // operand on gfx950, tools/micro/dppsem.hip, so it is not used.)  Every VGPR a DPP
+    // instruction reads is written at least two instructions earlier; a read or a wait
+    // between two rounds only lengthens those distances.
+    uint32_t t1, t2, kk, p, cc, dd, c2;
+    // order of the text: quad-times 0 .. 14 (bursts A and B after the first round of quad-times
+    // 0 and 8), n = 62, n = 63 (on the next block's KW0), F1, n = 64, F2, n = 65, F3
+    asm volatile(KRK_SHA8_QT(v67, v68, v69, v70, KRK_SHA8_BURST_A)
+                 KRK_SHA8_QT(v71, v72, v73, v74, "")
+                 KRK_SHA8_QT(v75, v76, v77, v78, "")
+                 KRK_SHA8_QT(v79, v80, v81, v82, "")
+                 KRK_SHA8_QT(v83, v84, v85, v86, "")
+                 KRK_SHA8_QT(v87, v88, v89, v90, "")
+                 KRK_SHA8_QT(v91, v92, v93, v94, "")
+                 KRK_SHA8_QT(v95, v96, v97, v98, "")
+                 KRK_SHA8_QT(v99, v100, v101, v102, KRK_SHA8_BURST_B)
+                 KRK_SHA8_QT(v103, v104, v105, v106, "")
+                 KRK_SHA8_QT(v107, v108, v109, v110, "")
+                 KRK_SHA8_QT(v111, v112, v113, v114, "")
+                 KRK_SHA8_QT(v115, v116, v117, v118, "")
+                 KRK_SHA8_QT(v119, v120, v121, v122, "")
+                 KRK_SHA8_QT(v123, v124, v125, v126, "")
+                 KRK_SHA8_ROUND_(R2, R1, R0, R3, "v127")
+                 KRK_SHA8_ROUND_(R3, R2, R1, R0, "v64")
+                 "v_sub_u32_e32 %[cc], %[a0], %[e0]\n\t"
+                 "v_sub_u32_e32 %[dd], %[a1], %[e1]\n\t"
+                 "v_add_u32_e32 %[R0], %[e0], %[R0]\n\t"
+                 "v_add_u32_e32 %[R3], %[e1], %[R3]\n\t"
+                 "v_mov_b32_dpp %[c2], %[cc] row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
+                 "v_add_u32_dpp %[z], %[dd], %[z] row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
+                 "v_add_u32_e32 %[R2], %[e2], %[R2]\n\t"
+                 "v_add_u32_e32 %[R1], %[e3], %[R1]\n\t"
+                 "v_add_u32_e32 %[z], %[e3], %[z]\n\t"
+                 "v_cmp_lt_u32_e32 vcc, %[i], %[mineE]\n\t"
+                 "v_cndmask_b32_e32 %[e0], %[e0], %[R0], vcc\n\t"
+                 "v_cndmask_b32_e32 %[e1], %[e1], %[R3], vcc\n\t"
+                 "v_cndmask_b32_e32 %[e2], %[e2], %[R2], vcc\n\t"
+                 "v_cndmask_b32_e32 %[e3], %[e3], %[R1], vcc\n\t"
+                 KRK_SHA8_ROUND_(R0, R3, R2, R1, "v65")
+                 "v_add_u32_e32 %[z], %[c2], %[z]\n\t"
+                 KRK_SHA8_ROUND_(R1, R0, R3, R2, "v66")
+                 "v_sub_u32_e32 %[z], %[z], %[a1]\n\t"
+                 "v_add_u32_e32 %[R0], %[a0], %[R0]\n\t"
+                 "v_add_u32_e32 %[R3], %[a1], %[R3]\n\t"
+                 "v_add_u32_e32 %[R2], %[a2], %[R2]\n\t"
+                 "v_add_u32_e32 %[R1], %[a3], %[R1]\n\t"
+                 "v_cmp_lt_u32_e32 vcc, %[i], %[mineA]\n\t"
+                 "v_cndmask_b32_e32 %[a0], %[a0], %[R0], vcc\n\t"
+                 "v_cndmask_b32_e32 %[a1], %[a1], %[R3], vcc\n\t"
+                 "v_cndmask_b32_e32 %[a2], %[a2], %[R2], vcc\n\t"
+                 "v_cndmask_b32_e32 %[a3], %[a3], %[R1], vcc\n\t"
+                 : [t1] "=&v"(t1), [t2] "=&v"(t2), [k] "=&v"(kk), [p] "=&v"(p), [cc] "=&v"(cc), [dd] "=&v"(dd),
+                   [c2] "=&v"(c2), [z] "+v"(z),
+                   [R0] "+v"(R0), [R1] "+v"(R1), [R2] "+v"(R2), [R3] "+v"(R3), [e0] "+v"(hE[0]),
+                   [e1] "+v"(hE[1]), [e2] "+v"(hE[2]), [e3] "+v"(hE[3]), [a0] "+v"(hA[0]), [a1] "+v"(hA[1]),
+                   [a2] "+v"(hA[2]), [a3] "+v"(hA[3]),
+                   // in flight on return (see INVARIANT above): valid only after the next wait A
+                   "+{v[64:67]}"(k[0]), "+{v[68:71]}"(k[1]), "+{v[72:75]}"(k[2]), "+{v[76:79]}"(k[3]),
+                   "+{v[80:83]}"(k[4]), "+{v[84:87]}"(k[5]), "+{v[88:91]}"(k[6]), "+{v[92:95]}"(k[7]),
+                   "+{v[96:99]}"(k[8])
+                 : KRK_SHA8_CONSTS, [i] "s"(i), [mineE] "v"(mineE), [mineA] "v"(mineA), [cb] "v"(cur),
+                   [nb] "v"(nxt), [co] "n"(kCurOff), [no] "n"(kNxtOff)
+                 : "vcc", "memory", "v100", "v101", "v102", "v103", "v104", "v105", "v106", "v107", "v108",
+                   "v109", "v110", "v111", "v112", "v113", "v114", "v115", "v116", "v117", "v118", "v119", "v120",
+                   "v121", "v122", "v123", "v124", "v125", "v126", "v127");
 }
+#undef KRK_SHA8_QT
+#undef KRK_SHA8_BURST_A
+#undef KRK_SHA8_BURST_B
+#undef KRK_SHA8_RD
 
 // Instruction-rounds 0, 1 of a stream's first block (E rounds 0, 1; A idles and its
 // two results are replaced by H1, H0: rounds2's start).
@@ -697,8 +704,8 @@ __device__ __forceinline__ void sha2_quad2(uint32_t& R0, uint32_t& R1, uint32_t&
                  : KRK_SHA2_CONSTS, [w1] "v"(w1), [w2] "v"(w2), [w3] "v"(w3), [w4] "v"(w4));
 }
 
-// The two-lane consumer's W read groups: as the eight-lane consumer's (three quads read
-// four ahead, twelve rounds a wait) instead of one read and one wait per four rounds.  Same-box A/B (profiles/r02/sha2_read_groups.jsonl): 16,384
+// The two-lane consumer's W read groups: as the eight-lane consumer's until round 7 (three
+// quads read four ahead, twelve rounds a wait) instead of one read and one wait per four rounds.  Same-box A/B (profiles/r02/sha2_read_groups.jsonl): 16,384
 // streams 49.7 -> 51.6 MB/s a stream, 8,192 streams 50.4 -> 51.9 (pairs were 0.5 % slower
 // than one read a quad).
 constexpr int kAhead2 = 4;
@@ -1167,7 +1174,9 @@ sha256_w8_kernel(const ShaJob* __restrict__ jobs, uint32_t n_jobs, uint8_t* __re
     const uint32_t binc = 32u, sinc = is_e ? uint32_t(kSlotWords) : 0u;
     // voff: this lane's offset of block i (E: slot base vslot + jj * 32; A: 0)
     uint32_t voff = 0, vslot = 0, slot = 0;
-    u32x4 kq[kAhead8] = {};
+    // LDS byte address of this lane's column in slot 0 (block8p reads with ds_read_b128 itself)
+    const uint32_t lbyte = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t*)ring + 4u * lbase;
+    u32x4 kq[kHeld8] = {};
     // Blocks pipelined (block8p): 64 instruction-rounds a block; each half's chaining
     // value lives on its own lanes (0 on the other half).
     uint32_t hE[4], hA[4];
@@ -1178,12 +1187,10 @@ sha256_w8_kernel(const ShaJob* __restrict__ jobs, uint32_t n_jobs, uint8_t* __re
     }
     const uint32_t mineE = is_e ? mine : 0u, mineA = is_e ? 0u : mine;
     uint32_t R0 = h[0], R3 = h[1], R2 = h[2], R1 = h[3], z = 0;
-    auto block = [&](uint32_t i, uint32_t cur, uint32_t nxt) {
-        block8p(R0, R1, R2, R3, z, hE, hA, mineE, mineA, i, ring, cur, nxt, c, kq);
-    };
     // kU blocks an iteration (a step's 8 blocks never straddle an iteration): one block
     // an iteration ran at 52.9 MB/s a stream, two at 55.0 (fewer taken branches and
-    // less loop bookkeeping per block); with the W read groups, four 59.1 vs two 58.8,
+    // less loop bookkeeping per block); with W read in groups of three quads (the form
+    // before the bursts of block8p), four 59.1 vs two 58.8,
     // eight 59.1 (profiles/r02/sha8_unroll.jsonl).
     constexpr uint32_t kU = KRK_SHA8_UNROLL;
     static_assert(kU == 1 || kU == 2 || kU == 4 || kU == 8, "blocks per iteration divide a step");
@@ -1191,7 +1198,7 @@ sha256_w8_kernel(const ShaJob* __restrict__ jobs, uint32_t n_jobs, uint8_t* __re
         if (kTiming == 0) __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
 #pragma unroll
-        for (int q = 0; q < kAhead8; ++q) kq[q] = *reinterpret_cast<const u32x4*>(ring + lbase + 256 * q);
+        for (int q = 0; q < kHeld8; ++q) kq[q] = *reinterpret_cast<const u32x4*>(ring + lbase + 256 * q);
         prologue8p(R0, R1, R2, R3, z, h, is_e, c, kq[0]);
     }
     for (uint32_t i = 0; i < nb; i += kU) {
@@ -1202,19 +1209,43 @@ sha256_w8_kernel(const ShaJob* __restrict__ jobs, uint32_t n_jobs, uint8_t* __re
         }
         const bool last = jj == kStep8 - kU;
         const uint32_t nvslot = slot == kRing8 - 1 ? 0u : vslot + sinc;
-        uint32_t o = voff;
-#pragma unroll
-        for (uint32_t u = 0; u < kU; ++u) {
-            const uint32_t on = (u == kU - 1 && last) ? nvslot : o + binc;
-            if (u == 0 || i + u < nb) block(i + u, lbase + o, lbase + on);
-            o = on;
+        // block u of the iteration sits 4 * binc * u bytes past cur, a constant offset of
+        // its reads; only the iteration's last block can have its successor in the next slot
+        const uint32_t cur = lbyte + 4u * voff;
+        voff = last ? nvslot : voff + kU * binc;
+        const uint32_t nxt = lbyte + 4u * voff;
+        auto block = [&](auto u) {
+            constexpr uint32_t kB = 4u * binc * decltype(u)::value;
+            if constexpr (decltype(u)::value == kU - 1) {
+                block8p<kB, 0>(R0, R1, R2, R3, z, hE, hA, mineE, mineA, i + u, cur, nxt, c, kq);
+            } else {
+                block8p<kB, kB + 4u * binc>(R0, R1, R2, R3, z, hE, hA, mineE, mineA, i + u, cur, cur, c, kq);
+            }
+        };
+        block(std::integral_constant<uint32_t, 0>{});  // past nb only in the wave's last iteration
+        if constexpr (kU > 1) if (i + 1 < nb) block(std::integral_constant<uint32_t, 1 % kU>{});
+        if constexpr (kU > 2) {
+            if (i + 2 < nb) block(std::integral_constant<uint32_t, 2 % kU>{});
+            if (i + 3 < nb) block(std::integral_constant<uint32_t, 3 % kU>{});
         }
-        voff = o;
+        if constexpr (kU > 4) {
+            if (i + 4 < nb) block(std::integral_constant<uint32_t, 4 % kU>{});
+            if (i + 5 < nb) block(std::integral_constant<uint32_t, 5 % kU>{});
+            if (i + 6 < nb) block(std::integral_constant<uint32_t, 6 % kU>{});
+            if (i + 7 < nb) block(std::integral_constant<uint32_t, 7 % kU>{});
+        }
         if (last) {
             slot = slot == kRing8 - 1 ? 0u : slot + 1;
             vslot = nvslot;
         }
     }
+    // the last block's read-ahead is still on its way to the pinned W registers
+    asm volatile("s_waitcnt lgkmcnt(0)"
+                 : "+{v[64:67]}"(kq[0]), "+{v[68:71]}"(kq[1]), "+{v[72:75]}"(kq[2]), "+{v[76:79]}"(kq[3]),
+                   "+{v[80:83]}"(kq[4]), "+{v[84:87]}"(kq[5]), "+{v[88:91]}"(kq[6]), "+{v[92:95]}"(kq[7]),
+                   "+{v[96:99]}"(kq[8])
+                 :
+                 : "memory");
 #pragma unroll
     for (int k = 0; k < 4; ++k) h[k] = is_e ? hE[k] : hA[k];
     if (live && pos == 0) {
