@@ -134,7 +134,7 @@ static_assert(sizeof(ShaJob) == 64, "ShaJob layout");
 hipError_t launch_digest_scatter(const uint8_t* rec, uint32_t n, uint8_t* digests, hipStream_t s);
 hipError_t launch_sha256(const ShaJob* jobs, uint32_t n_jobs, uint8_t* out_digest,
                          uint32_t* out_state, hipStream_t s);
-// Lanes per stream launch_sha256 uses for a batch of n_jobs streams (1 or 2).
+// Lanes per stream launch_sha256 uses for a batch of n_jobs streams (1, 2 or 8).
 int sha_lanes_for(uint32_t n_jobs);
 int sha_plan_for(uint32_t n_jobs);  // KRK_SHA_PLAN_* the next launch of n_jobs streams uses
 // One launch on a given plan whatever the process-wide setting (planner calibration).

@@ -172,9 +172,9 @@ sha256_multi_kernel(const ShaJob* __restrict__ jobs, uint32_t n_jobs, uint8_t* _
 // 4 slots) or kSlots2 slots (two lanes per stream, where each producer step
 // builds two blocks), see produce_step.
 constexpr int kSlots = 4;
-#define KRK_RING2 3  // two-lane ring slots (a ring one slot deeper measured 0.4 % slower, profiles/r03/c3_ring4_ab.txt)
-constexpr int kSlots2 = 2 * KRK_RING2;  // two lanes: block positions in the ring ...
-constexpr int kRing2 = kSlots2 / 2;     // ... in 3 slots, two blocks per slot (A / E columns)
+// two-lane ring slots (a ring one slot deeper measured 0.4 % slower, profiles/r03/c3_ring4_ab.txt)
+constexpr int kRing2 = 3;
+constexpr int kSlots2 = 2 * kRing2;  // two lanes: block positions in the ring, two blocks per slot (A / E columns)
 constexpr int kSlotWords = 64 * 64;  // 64 rounds x 64 lanes
 // eight lanes: 1 KiB of 1s past the all-1 slot (the A lanes' column walks one block ahead)
 constexpr uint32_t kOnesPad8 = 256;
@@ -193,9 +193,6 @@ __device__ __forceinline__ uint32_t kw_base(uint32_t slot, uint32_t col) { retur
 // (the E lanes their partner's, the A lanes the all-1 slot's) and its own column
 // for odd blocks: a bijection within each 16-lane row, so the ds_read_b128 stays
 // conflict-free.  3 slots + the all-1 slot = 64 KiB: two workgroups fit a CU.
-__device__ __forceinline__ uint32_t kw2_base(uint32_t b, bool is_e, uint32_t lane) {
-    return kw_base(is_e ? (b >> 1) % kRing2 : kRing2, (b & 1) ? lane : (lane ^ 15u));
-}
 
 __device__ __forceinline__ uint32_t job_blocks(const ShaJob& job) {
     const uint32_t nblk = (uint32_t)(job.len / 64);
@@ -208,6 +205,23 @@ __device__ __forceinline__ uint32_t job_blocks(const ShaJob& job) {
 __device__ __forceinline__ uint32_t block_bytes(const ShaJob& job, uint32_t b) {
     const uint64_t off = (uint64_t)b * 64;
     return off < job.len ? (uint32_t)min<uint64_t>(64, job.len - off) : 0u;
+}
+
+// Workgroup-uniform block count: the largest of the workgroup's kGroups pairs (every wave
+// passes the same barriers).  Stream `me` of pair g is job sbase + g * per + me; this
+// lane's own pair is grp and its count is mine.
+template <int kGroups>
+__device__ __forceinline__ uint32_t workgroup_blocks(const ShaJob* jobs, uint32_t n_jobs, uint32_t sbase, uint32_t per,
+                                                     uint32_t me, uint32_t grp, uint32_t mine) {
+    uint32_t nb = 0;
+#pragma unroll
+    for (int g = 0; g < kGroups; ++g) {
+        const uint32_t jj = sbase + g * per + me;
+        if (jj < n_jobs) nb = max(nb, g == (int)grp ? mine : job_blocks(jobs[jj]));
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) nb = max(nb, (uint32_t)__shfl_xor((int)nb, off, 64));
+    return __builtin_amdgcn_readfirstlane(nb);
 }
 
 // Issue the loads of block b into raw[]: the five 16-byte-aligned chunks from
@@ -437,7 +451,8 @@ __device__ __forceinline__ uint32_t two_lane_stream(uint32_t lane) {
     return (lane >> 4) * 8 + (two_lane_is_e(lane) ? 7 - (lane & 7) : (lane & 7));
 }
 
-// One instruction-round; the new x0 overwrites x3 (dead once P is formed) or NX.
+// One instruction-round; the new x0 overwrites x3 (dead once P is formed) or NX, so the
+// history registers rotate: in instruction-round n, x0 = R[n%4], x3 = R[(n+1)%4].
 // z for the NEXT round is formed here (its x3 is this round's x2) so that no DPP
 // reads a result of the instruction right before it (that costs ~8 cycles; see
 // tools/micro/sha2lane.hip: 38 cycles a round this way, 47 with z formed in-round).
@@ -453,7 +468,7 @@ __device__ __forceinline__ uint32_t two_lane_stream(uint32_t lane) {
     "v_add3_u32 %[" #NX "], %[t1], %[k], %[p]\n\t"
 
 struct TwoLaneConst {
-    uint32_t r1, r2, r3, ma, one_a;
+    uint32_t r1, r2, r3, ma;
 };
 
 #define KRK_SHA2_OPERANDS                                                                             \
@@ -492,30 +507,6 @@ struct TwoLaneConst {
     : [t1] "=&v"(t1), [t2] "=&v"(t2), [k] "=&v"(kk), [p] "=&v"(p), [z] "+v"(z), [R0] "+v"(R0), \
       [R1] "+v"(R1), [R2] "+v"(R2), [R3] "+v"(R3)
 #define KRK_SHA8_CONSTS [r1] "v"(c.r1), [ma] "v"(c.ma)
-
-// Instruction-rounds 4q..4q+3; W of rounds 4q+1..4q+4 (for the z's).  History
-// registers rotate: in instruction-round n, x0 = R[n%4], x3 = R[(n+1)%4].
-__device__ __forceinline__ void sha2_quad(uint32_t& R0, uint32_t& R1, uint32_t& R2, uint32_t& R3, uint32_t& z,
-                                          const TwoLaneConst& c, uint32_t w1, uint32_t w2, uint32_t w3,
-                                          uint32_t w4) {
-    uint32_t t1, t2, t3, kk, p;
-    asm volatile(KRK_SHA2_ROUND(R0, R3, R2, R1, w1)
-                 KRK_SHA2_ROUND(R1, R0, R3, R2, w2)
-                 KRK_SHA2_ROUND(R2, R1, R0, R3, w3)
-                 KRK_SHA2_ROUND(R3, R2, R1, R0, w4)
-                 KRK_SHA2_OPERANDS
-                 : KRK_SHA2_CONSTS, [w1] "v"(w1), [w2] "v"(w2), [w3] "v"(w3), [w4] "v"(w4));
-    (void)t3;
-}
-
-// The W read-ahead: a consumer reads KW quads kAhead quads before their use (quad q+1's
-// first W feeds quad q's last z, so its read must have landed when quad q starts: issued
-// one quad before its use it stalled ~230 cycles a block in round 1's one-block-a-step
-// two-lane consumer), and the next block's first kAhead quads during the last ones.
-#define KRK_SHA_AHEAD 3
-constexpr int kAhead = KRK_SHA_AHEAD;
-#define KRK_SHA8_UNROLL 4  // eight-lane consumer: blocks per loop iteration
-static_assert(kAhead >= 2 && kAhead <= 8, "read-ahead distance");
 
 // W delivery of the eight-lane consumer: the ds_read_b128 and the s_waitcnt of a block
 // sit INSIDE the block's one asm statement (block8p), so the compiler places none of its
@@ -567,7 +558,7 @@ constexpr int kHeld8 = 9;
 // Eight lanes a stream, blocks pipelined: the A quad runs rounds 62, 63 of block i
 // while the E quad already runs rounds 0, 1 of block i + 1, so a block costs 64
 // instruction-rounds instead of 66.  State crosses blocks in registers: R0..R3 (the
-// history, same register roles as rounds2), z, and each half's chaining value hE
+// history: in instruction-round n, x0 = R[n % 4]), z, and each half's chaining value hE
 // (E quads: H4..H7, 0 on A lanes) / hA (A quads: H2, H3, H0, H1, 0 on E lanes) --
 // masked to its own quad so that one unmasked add feeds one half forward and adds 0
 // to the other.  Per block (instruction-rounds n = 2 .. 65 of block i):
@@ -667,7 +658,7 @@ __device__ __forceinline__ void block8p(uint32_t& R0, uint32_t& R1, uint32_t& R2
 #undef KRK_SHA8_RD
 
 // Instruction-rounds 0, 1 of a stream's first block (E rounds 0, 1; A idles and its
-// two results are replaced by H1, H0: rounds2's start).
+// two results are replaced by H1, H0).
 __device__ __forceinline__ void prologue8p(uint32_t& R0, uint32_t& R1, uint32_t& R2, uint32_t& R3, uint32_t& z,
                                            const uint32_t h[4], bool is_e, const TwoLaneConst& c,
                                            const u32x4& k0) {
@@ -687,27 +678,14 @@ __device__ __forceinline__ void prologue8p(uint32_t& R0, uint32_t& R1, uint32_t&
     }
     R2 = is_e ? R2 : h[2];
 }
-// Two-lane counterparts (block2p, sha2_quad2, prologue2p): the same pipelined block on
-// the two-lane round (KRK_SHA2_ROUND, partner lane by row_mirror), 64 instruction-rounds
-// a block instead of rounds2's 66.  The two-lane round opens with its DPP add, so the
-// F2 compensation of z is folded into round 64's W operand (w1 + c2) instead of being
-// added between rounds 64 and 65.
-// Rounds n = 4j + 2 .. 4j + 5 of a two-lane block (block2p), the register roles of
-// instruction-rounds 2 .. 5: W operands are W[n + 1] for the z of the next round.
-__device__ __forceinline__ void sha2_quad2(uint32_t& R0, uint32_t& R1, uint32_t& R2, uint32_t& R3, uint32_t& z,
-                                           const TwoLaneConst& c, uint32_t w1, uint32_t w2, uint32_t w3,
-                                           uint32_t w4) {
-    uint32_t t1, t2, t3, kk, p;
-    asm volatile(KRK_SHA2_ROUND(R2, R1, R0, R3, w1) KRK_SHA2_ROUND(R3, R2, R1, R0, w2)
-                 KRK_SHA2_ROUND(R0, R3, R2, R1, w3) KRK_SHA2_ROUND(R1, R0, R3, R2, w4)
-                 KRK_SHA2_OPERANDS
-                 : KRK_SHA2_CONSTS, [w1] "v"(w1), [w2] "v"(w2), [w3] "v"(w3), [w4] "v"(w4));
-}
 
-// The two-lane consumer's W read groups: as the eight-lane consumer's until round 7 (three
-// quads read four ahead, twelve rounds a wait) instead of one read and one wait per four rounds.  Same-box A/B (profiles/r02/sha2_read_groups.jsonl): 16,384
-// streams 49.7 -> 51.6 MB/s a stream, 8,192 streams 50.4 -> 51.9 (pairs were 0.5 % slower
-// than one read a quad).
+// The two-lane consumer's W read groups: three quads read kAhead2 quads ahead and twelve
+// rounds a wait (sha2_dodec2: rounds n = 4j + 2 .. 4j + 13 of a block, W operands W[n + 1]
+// for the z of the next round) instead of one read and one wait per four rounds.  Same-box
+// A/B (profiles/r02/sha2_read_groups.jsonl): 16,384 streams 49.7 -> 51.6 MB/s a stream,
+// 8,192 streams 50.4 -> 51.9 (pairs were 0.5 % slower than one read a quad).  A read
+// issued only one quad before its use stalled ~230 cycles a block (quad q + 1's first W
+// feeds quad q's last z, so it must have landed when quad q starts).
 constexpr int kAhead2 = 4;
 __device__ __forceinline__ void sha2_dodec2(uint32_t& R0, uint32_t& R1, uint32_t& R2, uint32_t& R3, uint32_t& z,
                                             const TwoLaneConst& c, const u32x4& a, const u32x4& b, const u32x4& d,
@@ -726,28 +704,12 @@ __device__ __forceinline__ void sha2_dodec2(uint32_t& R0, uint32_t& R1, uint32_t
     (void)t3;
 }
 
-
-// Eight lanes a stream, blocks pipelined: the A quad runs rounds 62, 63 of block i
-// while the E quad already runs rounds 0, 1 of block i + 1, so a block costs 64
-// instruction-rounds instead of 66.  State crosses blocks in registers: R0..R3 (the
-// history, same register roles as rounds2), z, and each half's chaining value hE
-// (E quads: H4..H7, 0 on A lanes) / hA (A quads: H2, H3, H0, H1, 0 on E lanes) --
-// masked to its own quad so that one unmasked add feeds one half forward and adds 0
-// to the other.  Per block (instruction-rounds n = 2 .. 65 of block i):
-//   n = 2 .. 63: both halves (E round n, A round n - 2);
-//   F1 (E finished block i): R += hE (E's feed-forward); E's round 0 of block i + 1
-//      reads d through the cross add as A's raw a61, so its z also takes the A
-//      half's H3 (partner's hA[1], via DPP) and the feed-forward of h (hE[3]); A's
-//      rounds 62, 63 read e63, e64 through the cross add from registers E has just
-//      fed forward, so A's z gives back H5 now and H4 after n = 64;
-//      hE <- R where i < this stream's block count;
-//   n = 64: E round 0 of block i + 1 (W = its KW0 .. KW1), A round 62;
-//   F2: E's round 1 reads raw a62 as d: z += partner's hA[0] (H2); A: z -= H4
-//      (both in one register cc formed in F1);
-//   n = 65: E round 1, A round 63;
-//   F3 (A finished block i): A's round 0 of block i + 1 takes -d from z formed on raw
-//      a61: z -= hA[1]; R += hA; hA <- R where i < the block count.
-// A finished stream's lanes keep computing on garbage; their hE / hA stay frozen.
+// The two-lane counterpart of block8p: the same pipelined block (F1 .. F3 as described
+// there) on the two-lane round (KRK_SHA2_ROUND), the partner lane by row_mirror instead of
+// row_ror:8.  The two-lane round opens with its DPP add, so the F2 compensation of z is
+// folded into round 64's W operand (w1 + c2) instead of being added between rounds 64
+// and 65.  k: the first kAhead2 W quads, this block's on entry and the next block's on
+// return; cbase / nbase: LDS word offsets of quad 0 of the two blocks' columns.
 __device__ __forceinline__ void block2p(uint32_t& R0, uint32_t& R1, uint32_t& R2, uint32_t& R3, uint32_t& z,
                                         uint32_t hE[4], uint32_t hA[4], uint32_t mineE, uint32_t mineA,
                                         uint32_t i, const uint32_t* lds, uint32_t cbase, uint32_t nbase,
@@ -756,11 +718,12 @@ __device__ __forceinline__ void block2p(uint32_t& R0, uint32_t& R1, uint32_t& R2
     u32x4 wq[kRS];
 #pragma unroll
     for (int j = 0; j < kAhead2; ++j) wq[j] = k[j];
-    // Rounds n = 2 .. 61 in 15 asm blocks of four, n = 4j + 2 .. 4j + 5 (W: quad j's last
-    // word, quad j + 1's first three), each W read between two blocks -- two rounds into
-    // a W quad.  Issued right before a W quad's rounds a read cost ~16 cycles of the
-    // wave's stream, two rounds in ~8, its code bytes (tools/micro/sha8lds.hip,
-    // profiles/r02/micro_sha8lds.txt); and the read + its wait between two asm blocks
+    // Rounds n = 2 .. 61 in five asm statements of twelve (sha2_dodec2), n = 12m + 2 ..
+    // 12m + 13 (W: quad 3m's last word, quads 3m + 1, 3m + 2 whole, quad 3m + 3's first
+    // three), the three W reads of a group between two statements -- two rounds into a W
+    // quad.  Issued right before a W quad's rounds a read cost ~16 cycles of the wave's
+    // stream, two rounds in ~8, its code bytes (tools/micro/sha8lds.hip,
+    // profiles/r02/micro_sha8lds.txt); and the reads + their wait between two statements
     // are the two wait states the hazard recognizer would otherwise pad there.
     constexpr int RS = kAhead2 + 3;
     u32x4 wr[RS];
@@ -833,7 +796,7 @@ __device__ __forceinline__ void block2p(uint32_t& R0, uint32_t& R1, uint32_t& R2
 }
 
 // Instruction-rounds 0, 1 of a stream's first block (E rounds 0, 1; A idles and its
-// two results are replaced by H1, H0: rounds2's start).
+// two results are replaced by H1, H0).
 __device__ __forceinline__ void prologue2p(uint32_t& R0, uint32_t& R1, uint32_t& R2, uint32_t& R3, uint32_t& z,
                                            const uint32_t h[4], bool is_e, const TwoLaneConst& c,
                                            const u32x4& k0) {
@@ -865,20 +828,18 @@ __device__ __forceinline__ uint32_t wave_min(uint32_t v) {
     return __builtin_amdgcn_readfirstlane(v);
 }
 
-// kTiming (diagnostic variant 2 only, wrong digests): the producer idles and the
-// consumer runs its rounds on whatever the ring holds with no barriers -- the
-// consumer's issue-bound time per block, to price the producer/consumer sync.
-// kTwo: two lanes per stream (32 streams per workgroup, rounds2); the producer
-// is unchanged -- both lanes of a stream build the same schedule into their own
-// LDS column.
-// kTiming 2 (diagnostic variants 5/6, wrong digests): the consumer exits at once and
-// the producer runs alone (its barriers then count only itself) -- the producer's
-// time per block.
+// kTiming (diagnostic build only, WRONG digests; plan numbers in launch_sha256_plan's table):
+//   1 (plans 102 / 104): the producer idles and the consumer runs its rounds on whatever
+//     the ring holds with no barriers -- the consumer's issue-bound time per block, to
+//     price the producer/consumer sync;
+//   2 (plans 105 / 106): the consumer exits at once and the producer runs alone (its
+//     barriers then count only itself) -- the producer's time per block;
+//   3 (plan 107): as 2, and the producer issues no global loads.
 //
-// kTwo: the producer's A and E lanes of a stream build two different blocks per
-// step (even and odd), so the producer's 64 lanes all do distinct work: built one
-// block a step, it (47.6 MB/s a stream) could not keep up with the two-lane
-// consumer (50 MB/s a stream).
+// kTwo: two lanes per stream (32 streams a pair, block2p).  The producer's A and E lanes
+// of a stream build two different blocks per step (even and odd), so the producer's 64
+// lanes all do distinct work: built one block a step, it (47.6 MB/s a stream) could not
+// keep up with the two-lane consumer (50 MB/s a stream).
 //
 // kGroups = 2: two producer/consumer pairs in one 4-wave workgroup, each with its own
 // ring (128 KiB): the hardware puts the four waves of a workgroup on the four SIMDs
@@ -906,22 +867,12 @@ sha256_ws_kernel(const ShaJob* __restrict__ jobs, uint32_t n_jobs, uint8_t* __re
     ShaJob job{};
     if (live) job = jobs[j];
     const uint32_t mine = live ? job_blocks(job) : 0u;
-    // workgroup-uniform block count (every wave passes the same barriers)
-    uint32_t nb = 0;
-#pragma unroll
-    for (int g = 0; g < kGroups; ++g) {
-        const uint32_t jj = sbase + g * kPer + me;
-        if (jj < n_jobs) nb = max(nb, g == (int)grp ? mine : job_blocks(jobs[jj]));
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) nb = max(nb, (uint32_t)__shfl_xor((int)nb, off, 64));
-    nb = __builtin_amdgcn_readfirstlane(nb);
+    const uint32_t nb = workgroup_blocks<kGroups>(jobs, n_jobs, sbase, kPer, me, grp, mine);
 
     if (producer && kTiming == 1) return;
     if (!producer && kTiming >= 2) return;
     if (producer) {
-        // Two lanes per stream: the A lanes read W from the extra slot kRing2, all 1s
-        // (rounds2).
+        // Two lanes per stream: the A lanes read W from the extra slot kRing2, all 1s.
         if (kTwo) {
 #pragma unroll
             for (int q = 0; q < 16; ++q)
@@ -950,8 +901,8 @@ sha256_ws_kernel(const ShaJob* __restrict__ jobs, uint32_t n_jobs, uint8_t* __re
     } else if (kTwo) {
         const bool is_e = two_lane_is_e(lane);
         const uint32_t half = is_e ? 4u : 0u;
-        const TwoLaneConst c{is_e ? 6u : 2u, is_e ? 11u : 13u, is_e ? 25u : 22u, is_e ? 0u : ~0u, is_e ? 0u : 1u};
-        // h[k] = H[4 + k] on E lanes, H[k ^ 2] on A lanes (rounds2's register order).
+        const TwoLaneConst c{is_e ? 6u : 2u, is_e ? 11u : 13u, is_e ? 25u : 22u, is_e ? 0u : ~0u};
+        // h[k] = H[4 + k] on E lanes, H[k ^ 2] on A lanes (R0, R3, R2, R1 start as h[0 .. 3]).
         uint32_t h[4];
         if (live && (job.flags & kShaFromState)) {
 #pragma unroll
@@ -961,10 +912,8 @@ sha256_ws_kernel(const ShaJob* __restrict__ jobs, uint32_t n_jobs, uint8_t* __re
             for (int k = 0; k < 4; ++k) h[k] = is_e ? job.h[4 + k] : job.h[k ^ 2];  // no dynamic index: keeps job out of scratch
         }
         __builtin_amdgcn_s_setprio(3);
-        // Blocks every live lane still needs (wave-uniform): no per-lane masking there.
-        const uint32_t common = wave_min(live ? mine : ~0u);
-        // kw2_base without the per-block slot arithmetic: the loop runs one producer
-        // step (an even and an odd block, one slot) per iteration; vslot = the E
+        // The ring layout above without per-block slot arithmetic: the loop runs one
+        // producer step (an even and an odd block, one slot) per iteration; vslot = the E
         // lanes' slot offset (the A lanes always read the all-1 slot, vslot = 0).
         const uint32_t aoff = is_e ? 0u : uint32_t(kRing2) * kSlotWords;
         const uint32_t base_even = aoff + (lane ^ 15u) * 4, base_odd = aoff + lane * 4;
@@ -981,7 +930,6 @@ sha256_ws_kernel(const ShaJob* __restrict__ jobs, uint32_t n_jobs, uint8_t* __re
         }
         const uint32_t mineE = is_e ? mine : 0u, mineA = is_e ? 0u : mine;
         uint32_t R0 = h[0], R3 = h[1], R2 = h[2], R1 = h[3], z = 0;
-        (void)common;
         auto block = [&](uint32_t i, uint32_t cur, uint32_t nxt) {
             block2p(R0, R1, R2, R3, z, hE, hA, mineE, mineA, i, ring, cur, nxt, c, kq);
         };
@@ -1042,9 +990,9 @@ sha256_ws_kernel(const ShaJob* __restrict__ jobs, uint32_t n_jobs, uint8_t* __re
         for (uint32_t i = 0; i < nb; ++i) {
             // The consumer writes no LDS, so its barrier needs no release fence (no
             // lgkmcnt drain): the quads prefetched below stay in flight across it.
-            // Block i+1 is complete once this barrier has passed (the producer runs
-            // kDepth-1 >= 1 blocks ahead of it), and its slot is not rewritten
-            // before the barrier after next.
+            // Block i+1 is complete once this barrier has passed (the producer reaches
+            // barrier i only after building step i + kSlots - 1, see produce_step), and
+            // its slot is not rewritten before the barrier after next.
             if (kTiming == 0) __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
             if (i == 0) {
@@ -1059,6 +1007,7 @@ sha256_ws_kernel(const ShaJob* __restrict__ jobs, uint32_t n_jobs, uint8_t* __re
                 k0 = kw_quad(ring, (int)((i + 1) % kSlots), 0, lane);
                 k1 = kw_quad(ring, (int)((i + 1) % kSlots), 1, lane);
             }
+            // not a duplicate: i < common is wave-uniform, so those blocks skip the per-lane mask
             if (i < common) {
 #pragma unroll
                 for (int k = 0; k < 8; ++k) h[k] = x[k];
@@ -1118,15 +1067,7 @@ sha256_w8_kernel(const ShaJob* __restrict__ jobs, uint32_t n_jobs, uint8_t* __re
     ShaJob job{};
     if (live) job = jobs[j];
     const uint32_t mine = live ? job_blocks(job) : 0u;
-    uint32_t nb = 0;
-#pragma unroll
-    for (int g = 0; g < kGroups; ++g) {
-        const uint32_t jj = sbase + g * kPer + me;
-        if (jj < n_jobs) nb = max(nb, g == (int)grp ? mine : job_blocks(jobs[jj]));
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) nb = max(nb, (uint32_t)__shfl_xor((int)nb, off, 64));
-    nb = __builtin_amdgcn_readfirstlane(nb);
+    const uint32_t nb = workgroup_blocks<kGroups>(jobs, n_jobs, sbase, kPer, me, grp, mine);
 
     if (producer && kTiming == 1) return;
     if (producer) {
@@ -1155,8 +1096,8 @@ sha256_w8_kernel(const ShaJob* __restrict__ jobs, uint32_t n_jobs, uint8_t* __re
     const uint32_t half = is_e ? 4u : 0u;
     // this lane's Sigma rotation: E quads Sigma1 (6, 11, 25), A quads Sigma0 (2, 13, 22)
     const uint32_t r1 = is_e ? (pos == 1 ? 11u : pos == 2 ? 25u : 6u) : (pos == 1 ? 13u : pos == 2 ? 22u : 2u);
-    const TwoLaneConst c{r1, 0u, 0u, is_e ? 0u : ~0u, is_e ? 0u : 1u};
-    uint32_t h[4];  // H[4 + k] on E lanes, H[k ^ 2] on A lanes (rounds2's register order)
+    const TwoLaneConst c{r1, 0u, 0u, is_e ? 0u : ~0u};
+    uint32_t h[4];  // H[4 + k] on E lanes, H[k ^ 2] on A lanes (R0, R3, R2, R1 start as h[0 .. 3])
     if (live && (job.flags & kShaFromState)) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) h[k] = out_state[8 * (uint64_t)job.out + half + (is_e ? k : k ^ 2)];
@@ -1187,13 +1128,13 @@ sha256_w8_kernel(const ShaJob* __restrict__ jobs, uint32_t n_jobs, uint8_t* __re
     }
     const uint32_t mineE = is_e ? mine : 0u, mineA = is_e ? 0u : mine;
     uint32_t R0 = h[0], R3 = h[1], R2 = h[2], R1 = h[3], z = 0;
-    // kU blocks an iteration (a step's 8 blocks never straddle an iteration): one block
+    // Four blocks an iteration (a step's 8 blocks never straddle an iteration): one block
     // an iteration ran at 52.9 MB/s a stream, two at 55.0 (fewer taken branches and
     // less loop bookkeeping per block); with W read in groups of three quads (the form
     // before the bursts of block8p), four 59.1 vs two 58.8,
     // eight 59.1 (profiles/r02/sha8_unroll.jsonl).
-    constexpr uint32_t kU = KRK_SHA8_UNROLL;
-    static_assert(kU == 1 || kU == 2 || kU == 4 || kU == 8, "blocks per iteration divide a step");
+    constexpr uint32_t kU = 4;
+    static_assert(kStep8 % kU == 0, "blocks per iteration divide a step");
     if (nb) {  // step 0's barrier, the first quads, and (pipelined) rounds 0, 1 of block 0
         if (kTiming == 0) __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
@@ -1214,26 +1155,16 @@ sha256_w8_kernel(const ShaJob* __restrict__ jobs, uint32_t n_jobs, uint8_t* __re
         const uint32_t cur = lbyte + 4u * voff;
         voff = last ? nvslot : voff + kU * binc;
         const uint32_t nxt = lbyte + 4u * voff;
-        auto block = [&](auto u) {
-            constexpr uint32_t kB = 4u * binc * decltype(u)::value;
-            if constexpr (decltype(u)::value == kU - 1) {
-                block8p<kB, 0>(R0, R1, R2, R3, z, hE, hA, mineE, mineA, i + u, cur, nxt, c, kq);
-            } else {
-                block8p<kB, kB + 4u * binc>(R0, R1, R2, R3, z, hE, hA, mineE, mineA, i + u, cur, cur, c, kq);
-            }
-        };
-        block(std::integral_constant<uint32_t, 0>{});  // past nb only in the wave's last iteration
-        if constexpr (kU > 1) if (i + 1 < nb) block(std::integral_constant<uint32_t, 1 % kU>{});
-        if constexpr (kU > 2) {
-            if (i + 2 < nb) block(std::integral_constant<uint32_t, 2 % kU>{});
-            if (i + 3 < nb) block(std::integral_constant<uint32_t, 3 % kU>{});
-        }
-        if constexpr (kU > 4) {
-            if (i + 4 < nb) block(std::integral_constant<uint32_t, 4 % kU>{});
-            if (i + 5 < nb) block(std::integral_constant<uint32_t, 5 % kU>{});
-            if (i + 6 < nb) block(std::integral_constant<uint32_t, 6 % kU>{});
-            if (i + 7 < nb) block(std::integral_constant<uint32_t, 7 % kU>{});
-        }
+        constexpr uint32_t kB = 4u * binc;  // bytes from a block's column to the next block's
+        // Inside a lambda on purpose: called straight from the loop body the same four
+        // statements get other VGPR numbers; through the by-reference captures the code
+        // is byte for byte the one that was measured.
+        [&] {  // block 0 is past nb only in the wave's last iteration
+            block8p<0, kB>(R0, R1, R2, R3, z, hE, hA, mineE, mineA, i, cur, cur, c, kq);
+            if (i + 1 < nb) block8p<kB, 2 * kB>(R0, R1, R2, R3, z, hE, hA, mineE, mineA, i + 1, cur, cur, c, kq);
+            if (i + 2 < nb) block8p<2 * kB, 3 * kB>(R0, R1, R2, R3, z, hE, hA, mineE, mineA, i + 2, cur, cur, c, kq);
+            if (i + 3 < nb) block8p<3 * kB, 0>(R0, R1, R2, R3, z, hE, hA, mineE, mineA, i + 3, cur, nxt, c, kq);
+        }();
         if (last) {
             slot = slot == kRing8 - 1 ? 0u : slot + 1;
             vslot = nvslot;
@@ -1267,19 +1198,96 @@ sha256_w8_kernel(const ShaJob* __restrict__ jobs, uint32_t n_jobs, uint8_t* __re
     }
 }
 
-// Launch plans.  Production (every plan bit-exact):
-//   KRK_SHA_PLAN_1LANE        one lane per stream, one producer/consumer pair per workgroup
-//   KRK_SHA_PLAN_2LANE        two lanes per stream, one pair per workgroup
-//   KRK_SHA_PLAN_1LANE_2PAIR  one lane, two pairs per 4-wave workgroup
-//   KRK_SHA_PLAN_2LANE_2PAIR  two lanes, two pairs per workgroup
-//   KRK_SHA_PLAN_8LANE        eight lanes per stream (sha256_w8_kernel), one pair per workgroup
-//   KRK_SHA_PLAN_8LANE_2PAIR  eight lanes, two pairs per workgroup
-//   KRK_SHA_PLAN_AUTO         auto_plan() below
-// The plan is process-wide state set by krk_set_sha_plan (or KRK_SHA_PLAN read once,
-// at the first launch); it is not re-read per launch.  The timing diagnostics
-// (rounds-only consumer, producer-only, no-load producer: WRONG digests) and the
-// one-lane-does-everything kernel exist only in the diagnostic build (make diag,
-// -DKRK_DIAG), selected there with plan numbers 100 + the old variant number.
+// One launch of a producer/consumer kernel: kPairs pairs a workgroup (two waves each), each
+// with kPairLds bytes of dynamic LDS, over kPairStreams streams.
+using ShaLaunch = hipError_t (*)(const ShaJob*, uint32_t, uint8_t*, uint32_t*, hipStream_t);
+
+template <auto kKernel, size_t kPairLds, uint32_t kPairStreams, int kPairs>
+static hipError_t launch_pairs(const ShaJob* jobs, uint32_t n_jobs, uint8_t* out_digest, uint32_t* out_state,
+                               hipStream_t s) {
+    constexpr size_t lds = kPairLds * kPairs;
+    constexpr uint32_t per = kPairStreams * kPairs;
+    static std::once_flag once;  // host threads may launch concurrently (re-entrant C ABI)
+    static hipError_t attr_err = hipSuccess;
+    std::call_once(once, [] {
+        attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(kKernel),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    });
+    if (attr_err != hipSuccess) return attr_err;
+    if (const hipError_t p_ = launch_precheck(); p_ != hipSuccess) return p_;
+    hipLaunchKernelGGL(kKernel, dim3((n_jobs + per - 1) / per), dim3(128 * kPairs), lds, s, jobs, n_jobs, out_digest,
+                       out_state);
+    return hipGetLastError();
+}
+
+template <int kLanes, int kPairs, int kTiming>
+static hipError_t launch_lanes(const ShaJob* jobs, uint32_t n_jobs, uint8_t* out_digest, uint32_t* out_state,
+                               hipStream_t s) {
+    static_assert(kLanes == 1 || kLanes == 2 || kLanes == 8, "lanes a stream");
+    if constexpr (kLanes == 8) {
+        // 3 ring slots + the all-1 slot + its pad: 65 KiB a pair
+        return launch_pairs<&sha256_w8_kernel<kTiming, kPairs>, (4 * kSlotWords + kOnesPad8) * 4, 8, kPairs>(
+            jobs, n_jobs, out_digest, out_state, s);
+    } else {
+        constexpr bool kTwo = kLanes == 2;  // 64 KiB a pair
+        return launch_pairs<&sha256_ws_kernel<kTiming, kTwo, kPairs>, size_t(kTwo ? kRing2 + 1 : kSlots) * kSlotWords * 4,
+                            kTwo ? 32 : 64, kPairs>(jobs, n_jobs, out_digest, out_state, s);
+    }
+}
+
+#ifdef KRK_DIAG
+static hipError_t launch_multi(const ShaJob* jobs, uint32_t n_jobs, uint8_t* out_digest, uint32_t* out_state,
+                                  hipStream_t s) {
+    if (const hipError_t p_ = launch_precheck(); p_ != hipSuccess) return p_;
+    hipLaunchKernelGGL(sha256_multi_kernel, dim3((n_jobs + 63) / 64), dim3(64), 0, s, jobs, n_jobs, out_digest,
+                       out_state);
+    return hipGetLastError();
+}
+#endif
+
+// Launch plans: id, lanes a stream, producer/consumer pairs a workgroup, kTiming of the
+// kernel.  Every production plan is bit-exact; KRK_SHA_PLAN_AUTO is no row, auto_plan()
+// below picks one.  The timing diagnostics (kTiming != 0: WRONG digests, see
+// sha256_ws_kernel and sha256_w8_kernel) and the one-lane-does-everything kernel exist
+// only in the diagnostic build (make diag, -DKRK_DIAG), as plans 100 .. 108.
+struct ShaPlan {
+    int id, lanes, pairs, timing;
+    ShaLaunch launch;
+};
+template <int kLanes, int kPairs, int kTiming = 0>
+constexpr ShaPlan sha_plan_row(int id) {
+    return {id, kLanes, kPairs, kTiming, &launch_lanes<kLanes, kPairs, kTiming>};
+}
+constexpr ShaPlan kShaPlans[] = {
+    sha_plan_row<1, 1>(KRK_SHA_PLAN_1LANE),
+    sha_plan_row<2, 1>(KRK_SHA_PLAN_2LANE),
+    sha_plan_row<1, 2>(KRK_SHA_PLAN_1LANE_2PAIR),
+    sha_plan_row<2, 2>(KRK_SHA_PLAN_2LANE_2PAIR),
+    sha_plan_row<8, 1>(KRK_SHA_PLAN_8LANE),
+    sha_plan_row<8, 2>(KRK_SHA_PLAN_8LANE_2PAIR),
+#ifdef KRK_DIAG
+    {100, 1, 1, 0, &launch_multi},  // sha256_multi_kernel: one lane loads, schedules and runs the rounds
+    sha_plan_row<1, 1>(101),
+    sha_plan_row<1, 1, 1>(102),  // rounds-only consumer
+    sha_plan_row<2, 1>(103),
+    sha_plan_row<2, 1, 1>(104),  // rounds-only consumer
+    sha_plan_row<1, 1, 2>(105),  // producer only
+    sha_plan_row<2, 1, 2>(106),  // producer only
+    sha_plan_row<2, 1, 3>(107),  // producer only, no global loads
+    sha_plan_row<8, 1, 1>(108),  // rounds-only consumer
+#endif
+};
+
+static const ShaPlan* find_plan(int id) {
+    for (const ShaPlan& p : kShaPlans)
+        if (p.id == id) return &p;
+    return nullptr;
+}
+
+bool sha_plan_valid(int p) { return p == KRK_SHA_PLAN_AUTO || find_plan(p); }
+
+// The plan is process-wide state set by krk_set_sha_plan (or KRK_SHA_PLAN read once, at
+// the first launch); it is not re-read per launch.
 static std::atomic<int> g_sha_plan{-1};
 
 static int sha_plan() {
@@ -1293,22 +1301,8 @@ static int sha_plan() {
     return g_sha_plan.load(std::memory_order_relaxed);
 }
 
-bool sha_plan_valid(int p) {
-    if (p >= KRK_SHA_PLAN_AUTO && p <= KRK_SHA_PLAN_8LANE_2PAIR) return true;
-#ifdef KRK_DIAG
-    return p >= 100 && p <= 108;
-#else
-    return false;
-#endif
-}
-
 void set_sha_plan(int p) { g_sha_plan.store(p, std::memory_order_relaxed); }
 
-// Streams up to which two lanes per stream win: two two-lane workgroups (64 KiB of
-// LDS each) per CU.  Measured (tools/probe_perf.py, profiles/r01/sha_compact_ring.jsonl):
-// 8,192 streams 47.9 MB/s a stream two-lane vs 35.9 one-lane; 16,384 streams 37.3 vs
-// 35.5 (two workgroups then share a CU's SIMDs).  Beyond that the two-lane grid would
-// run in waves of workgroups.
 static uint32_t device_cus() {
     static uint32_t n = [] {
         int dev = 0, cus = 256;
@@ -1320,17 +1314,20 @@ static uint32_t device_cus() {
     }();
     return n;
 }
-static uint32_t two_lane_max_streams() { return device_cus() * 64u; }
 
 // Automatic plan: eight lanes a stream up to 16 x CUs streams (two 64 KiB pairs per
 // CU; at 4,096 streams 52.6 MB/s a stream vs 49.8 with two lanes, at 8,192 the
 // eight-lane grid runs in two waves of workgroups and halves, tools/probe_perf.py);
 // two lanes, one pair per workgroup up to 32 x CUs; two lanes, two pairs per
 // workgroup up to 64 x CUs; one lane, two pairs per workgroup beyond.
+// 64 x CUs is two two-lane workgroups (64 KiB of LDS each) per CU.  Measured
+// (tools/probe_perf.py, profiles/r01/sha_compact_ring.jsonl): 8,192 streams 47.9 MB/s a
+// stream two-lane vs 35.9 one-lane; 16,384 streams 37.3 vs 35.5 (two workgroups then
+// share a CU's SIMDs).  Beyond that the two-lane grid would run in waves of workgroups.
 static int auto_plan(uint32_t n_jobs) {
     if (n_jobs <= device_cus() * 16u) return KRK_SHA_PLAN_8LANE;
     if (n_jobs <= device_cus() * 32u) return KRK_SHA_PLAN_2LANE;
-    return n_jobs <= two_lane_max_streams() ? KRK_SHA_PLAN_2LANE_2PAIR : KRK_SHA_PLAN_1LANE_2PAIR;
+    return n_jobs <= device_cus() * 64u ? KRK_SHA_PLAN_2LANE_2PAIR : KRK_SHA_PLAN_1LANE_2PAIR;
 }
 
 static int resolve_plan(uint32_t n_jobs) {
@@ -1338,56 +1335,11 @@ static int resolve_plan(uint32_t n_jobs) {
     return p == KRK_SHA_PLAN_AUTO ? auto_plan(n_jobs) : p;
 }
 
-static bool plan_two_lanes(int p) {
-    return p == KRK_SHA_PLAN_2LANE || p == KRK_SHA_PLAN_2LANE_2PAIR || p == 103 || p == 104 || p == 106 ||
-           p == 107;
-}
-
-static bool plan_eight_lanes(int p) { return p == KRK_SHA_PLAN_8LANE || p == KRK_SHA_PLAN_8LANE_2PAIR || p == 108; }
-
 int sha_plan_for(uint32_t n_jobs) { return resolve_plan(n_jobs); }
 
 int sha_lanes_for(uint32_t n_jobs) {
-    const int p = resolve_plan(n_jobs);
-    return plan_eight_lanes(p) ? 8 : plan_two_lanes(p) ? 2 : 1;
-}
-
-template <int kTiming, int kGroups>
-static hipError_t launch_w8(const ShaJob* jobs, uint32_t n_jobs, uint8_t* out_digest, uint32_t* out_state,
-                            hipStream_t s) {
-    constexpr size_t lds = size_t(kGroups) * (4 * kSlotWords + kOnesPad8) * 4;  // 3 ring slots + the all-1 slot: 65 KiB a pair
-    auto* k = &sha256_w8_kernel<kTiming, kGroups>;
-    static std::once_flag once;
-    static hipError_t attr_err = hipSuccess;
-    std::call_once(once, [k] {
-        attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)lds);
-    });
-    if (attr_err != hipSuccess) return attr_err;
-    constexpr uint32_t per = 8u * kGroups;
-    if (const hipError_t p_ = launch_precheck(); p_ != hipSuccess) return p_;
-    hipLaunchKernelGGL(k, dim3((n_jobs + per - 1) / per), dim3(128 * kGroups), lds, s, jobs, n_jobs, out_digest,
-                       out_state);
-    return hipGetLastError();
-}
-
-template <int kTiming, bool kTwo, int kGroups>
-static hipError_t launch_ws(const ShaJob* jobs, uint32_t n_jobs, uint8_t* out_digest, uint32_t* out_state,
-                            hipStream_t s) {
-    constexpr size_t lds = size_t(kGroups) * size_t(kTwo ? kRing2 + 1 : kSlots) * kSlotWords * 4;  // 64 KiB a pair
-    auto* k = &sha256_ws_kernel<kTiming, kTwo, kGroups>;
-    static std::once_flag once;  // host threads may launch concurrently (re-entrant C ABI)
-    static hipError_t attr_err = hipSuccess;
-    std::call_once(once, [k] {
-        attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)lds);
-    });
-    if (attr_err != hipSuccess) return attr_err;
-    constexpr uint32_t per = (kTwo ? 32u : 64u) * kGroups;
-    if (const hipError_t p_ = launch_precheck(); p_ != hipSuccess) return p_;
-    hipLaunchKernelGGL(k, dim3((n_jobs + per - 1) / per), dim3(128 * kGroups), lds, s, jobs, n_jobs, out_digest,
-                       out_state);
-    return hipGetLastError();
+    const ShaPlan* p = find_plan(resolve_plan(n_jobs));
+    return p ? p->lanes : 1;
 }
 
 hipError_t launch_sha256(const ShaJob* jobs, uint32_t n_jobs, uint8_t* out_digest,
@@ -1401,32 +1353,8 @@ hipError_t launch_sha256_plan(int plan, const ShaJob* jobs, uint32_t n_jobs, uin
     if (!n_jobs) return hipSuccess;
     t_launch_plan = plan;
     t_launch_units = n_jobs;
-    switch (plan) {
-        case KRK_SHA_PLAN_1LANE: return launch_ws<0, false, 1>(jobs, n_jobs, out_digest, out_state, s);
-        case KRK_SHA_PLAN_2LANE: return launch_ws<0, true, 1>(jobs, n_jobs, out_digest, out_state, s);
-        case KRK_SHA_PLAN_1LANE_2PAIR: return launch_ws<0, false, 2>(jobs, n_jobs, out_digest, out_state, s);
-        case KRK_SHA_PLAN_2LANE_2PAIR: return launch_ws<0, true, 2>(jobs, n_jobs, out_digest, out_state, s);
-        case KRK_SHA_PLAN_8LANE: return launch_w8<0, 1>(jobs, n_jobs, out_digest, out_state, s);
-        case KRK_SHA_PLAN_8LANE_2PAIR: return launch_w8<0, 2>(jobs, n_jobs, out_digest, out_state, s);
-#ifdef KRK_DIAG
-        // diagnostics (WRONG digests except 100): rounds-only consumer (102 one lane, 104 two
-        // lanes), producer-only (105 / 106), producer without global loads (107)
-        case 100:
-            if (const hipError_t p_ = launch_precheck(); p_ != hipSuccess) return p_;
-            hipLaunchKernelGGL(sha256_multi_kernel, dim3((n_jobs + 63) / 64), dim3(64), 0, s, jobs, n_jobs,
-                               out_digest, out_state);
-            return hipGetLastError();
-        case 101: return launch_ws<0, false, 1>(jobs, n_jobs, out_digest, out_state, s);
-        case 102: return launch_ws<1, false, 1>(jobs, n_jobs, out_digest, out_state, s);
-        case 103: return launch_ws<0, true, 1>(jobs, n_jobs, out_digest, out_state, s);
-        case 104: return launch_ws<1, true, 1>(jobs, n_jobs, out_digest, out_state, s);
-        case 105: return launch_ws<2, false, 1>(jobs, n_jobs, out_digest, out_state, s);
-        case 106: return launch_ws<2, true, 1>(jobs, n_jobs, out_digest, out_state, s);
-        case 107: return launch_ws<3, true, 1>(jobs, n_jobs, out_digest, out_state, s);
-        case 108: return launch_w8<1, 1>(jobs, n_jobs, out_digest, out_state, s);  // eight-lane rounds only
-#endif
-        default: return hipErrorInvalidValue;
-    }
+    const ShaPlan* p = find_plan(plan);
+    return p ? p->launch(jobs, n_jobs, out_digest, out_state, s) : hipErrorInvalidValue;
 }
 
 // Host-offloaded digests into their batch slots (offload.cpp): record j = 4-byte blob

@@ -622,6 +622,18 @@ def test_public_header_is_the_bound_surface():
     assert called <= pub, called - pub
 
 
+def test_sha_plan_range_of_the_production_library():
+    """krk_set_sha_plan takes AUTO and the six production plans; the diagnostic plans
+    (100 .. 108) exist only in the KRK_DIAG build, so the production library refuses them."""
+    try:
+        for p in range(0, 7):
+            assert lib.krk_set_sha_plan(p) == 0, p
+        for p in (-1, 7, 99, 100, 108):
+            assert lib.krk_set_sha_plan(p) == _capi.KRK_EINVAL, p
+    finally:
+        check(lib.krk_set_sha_plan(0))
+
+
 def _set_rates(stream, host_sha, h2d, cus=256):
     r = _capi.krk_planner_rates()
     for k, v in enumerate(stream):

@@ -39,12 +39,10 @@ C_CASES = {
 def test_group_c_every_way_up(gpu, tmp_path, monkeypatch, name, leg):
     case = C_CASES[name](M.leg_align(leg))
     files_b = name == "B" and leg.startswith("files")
-    # B's files: 17,084 of them -- left out where the disk takes more than a second to write them; a process's
-    # descriptor budget may cap the live files below KRK_LIVE_CAP
-    bad = M.run_leg(case, leg, tmp_path, monkeypatch.setenv, lower_cap_ok=files_b, max_write_s=1.0 if files_b else None)
-    if bad is None:
-        pytest.skip("writing 17,084 files took more than a second")
-    _report(bad)
+    # B's files: 17,084 of them (5 MB, a second or two to write; the leg runs however long the disk takes, a skip
+    # by the clock made it come and go with the load of the machine); a process's descriptor budget may cap the
+    # live files below KRK_LIVE_CAP
+    _report(M.run_leg(case, leg, tmp_path, monkeypatch.setenv, lower_cap_ok=files_b))
 
 
 @pytest.mark.parametrize("ring", [2, 4])

@@ -628,17 +628,15 @@ class MemSource:
 
 
 class FileSource:
-    """The case's blobs as files of one directory; write_s: the seconds writing them took."""
+    """The case's blobs as files of one directory."""
 
     def __init__(self, case, directory):
-        t0 = time.perf_counter()
         self.paths = []
         for i in range(case.n):
             p = os.path.join(str(directory), "w%05d" % i)
             with open(p, "wb") as f:
                 f.write(memoryview(blob_bytes(case, i)))
             self.paths.append(p)
-        self.write_s = time.perf_counter() - t0
 
     def close(self):
         pass
@@ -727,12 +725,11 @@ def leg_align(leg):
     return 4096 if leg in DIRECT_LEGS else 64
 
 
-def run_leg(case, leg, directory, setenv, ring=RING, lower_cap_ok=False, max_write_s=None):
+def run_leg(case, leg, directory, setenv, ring=RING, lower_cap_ok=False):
     """`case` through one way up: every entry point of that way, whole-array comparison and the call statistics.
     setenv(name, value) sets the environment for the calls (read per call).  Returns the mismatches.
     lower_cap_ok: a file batch may run under a lower live cap than KRK_LIVE_CAP (the descriptor lease caps it by the
-    process's descriptor budget); the replay then takes the cap the call reports.  max_write_s: None is returned,
-    and nothing run, when writing the case's files took longer."""
+    process's descriptor budget); the replay then takes the cap the call reports."""
     from kraken_amd._capi import check, lib
     setenv("KRK_WINDOW_MB", str(case.window_mb))
     setenv("KRK_LIVE_CAP", str(case.cap))
@@ -743,8 +740,6 @@ def run_leg(case, leg, directory, setenv, ring=RING, lower_cap_ok=False, max_wri
         setenv("KRK_FILE_DIRECT", "0" if leg == "files" else "1")
         setenv("KRK_FILE_AIO", "0" if leg == "files_sync" else "1")
         src = FileSource(case, directory)
-        if max_write_s is not None and src.write_s > max_write_s:
-            return None
         out = call("metainfo_digest_files", case, src)
         st = last_call()
         if lower_cap_ok and st["max_live"] < min(case.cap, case.n):
