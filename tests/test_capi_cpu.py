@@ -791,7 +791,6 @@ def test_tail_ring_slot_held_until_its_crc_is_queued():
     CRC; the slot must not be regenerated until the CRC is queued and its event done -- the
     round-6 GPU failure was a 1 MiB-piece run whose ring wrapped inside one window wait and
     overwrote pieces whose CRCs had not run (wrong sums, right digests)."""
-    import threading
     from kraken_amd import windowed as WN
 
     class Buf:
@@ -827,26 +826,21 @@ def test_tail_ring_slot_held_until_its_crc_is_queued():
             self.fills.extend(int(p) for p in ptr)
 
     D = FakeD()
-    r = WN.TailHandoffRun.__new__(WN.TailHandoffRun)
-    import time
-    r.D, r.H, r.ring, r.piece, r._clock, r._gen_wait = D, 1, 2, 64, time.perf_counter, [0.0, 0.0]
-    r.hbuf, r.slot_ev, r.copy_s = [[Buf(0x9000), Buf(0xA000)]], [[C.c_void_p(1), C.c_void_p(2)]], C.c_void_p()
-    r.piece_s = C.c_void_p()
-    r.ids = np.arange(4, dtype=np.uint64)
-    r.gen_s = C.c_void_p()
-    r.tbuf = [[Buf(0x1000), Buf(0x2000)]]
-    r._cv = threading.Condition(threading.Lock())
-    r._to_gen = [[(0, o, 64, 0) for o in range(0, 6 * 64, 64)]]
-    r._ready, r._pending, r._tail_pieces = [[]], [], 0
-    r._slot_used, r._slot_crc, r._next_slot = [[False, False]], [[None, None]], [0]
+    r = WN.TailHandoffRun.__new__(WN.TailHandoffRun)  # what _service reads: the device, the slots, the run's state
+    r.D, r.ids = D, np.arange(4, dtype=np.uint64)
+    r.tbuf, r.hbuf = [[Buf(0x1000), Buf(0x2000)]], [[Buf(0x9000), Buf(0xA000)]]
+    r.slot_ev, r.copy_s, r.piece_s = [[C.c_void_p(1), C.c_void_p(2)]], C.c_void_p(), C.c_void_p()
+    r._st = WN._TailState(1, 2, 4)  # one thread, a ring of two slots
+    ring = r._st.rings
+    ring.to_gen[0] = [(0, o, 64, 0) for o in range(0, 6 * 64, 64)]
     assert len(r._service()) == 2  # both slots filled
-    r._ready[0].clear()
-    r._slot_used[0] = [False, False]  # the thread copied both down ...
+    ring.ready[0].clear()
+    ring.slot_used[0] = [False, False]  # the thread copied both down ...
     assert r._service() == [] and D.fills == [0x1000, 0x2000]  # ... but no CRC is queued yet
-    take = r._pending[:]
-    r._pending.clear()  # what _flush_crcs does, then _release with the event after it
+    take = ring.take_pending()  # what _flush_crcs does, then release with the event after it
+    assert len(take) == 2
     ev = C.c_void_p(77)
-    r._release(take, ev)
+    ring.release(take, ev)
     assert r._service() == []  # queued, not done
     D.lib.done[77] = 1
     assert len(r._service()) == 2 and D.fills[2:] == [0x1000, 0x2000]

@@ -70,6 +70,34 @@ def test_windowed_c3_matches_one_shot_and_oracle(one_shot, orc, window_gib, cap,
         assert np.array_equal(sums[a:a + int(counts1[i])], orc.calc_piece_sums(data, P)[1]), i
 
 
+def test_windowed_run_again_with_a_fresh_batch(gpu, orc):
+    """What the bench's warm-up does: run(), a fresh ChunkedBatch assigned to wr.cb, run()
+    again on the same WindowedRun (its buffers and streams reused).  48 blobs
+    of 0.2-2 MB under a live cap of 16 and 4 MiB windows: more than a dozen windows, most
+    blobs admitted late.  Both runs equal hashlib and the oracle's piece sums for every blob."""
+    n, p = 48, 256 << 10
+    lens = c3_lengths(n, scale=512)
+    ids = [(3 << 40) + i for i in range(n)]
+    wr = WindowedRun(D, ids, lens, p, 4 << 20, cap=16)
+    assert len(wr.wins) > 12 and max(len(w[0]) for w in wr.wins) <= 16 < n
+    want = []
+    for i in range(n):
+        data = orc.synth(ids[i], lens[i])
+        want.append((hashlib.sha256(data.tobytes()).digest(), orc.calc_piece_sums(data, p)[1]))
+    for rep in range(2):
+        if rep:
+            wr.cb = D.ChunkedBatch(lens, p)
+        wr.run()
+        cb = wr.cb
+        dg = cb.digests.to_host(np.uint8, 32 * n).reshape(-1, 32)
+        sums = cb.sums.to_host(np.uint32, cb.total_pieces)
+        for i, (digest, ref) in enumerate(want):
+            assert bytes(dg[i]) == digest, (rep, i)
+            a = int(cb.sums_off[i])
+            assert np.array_equal(sums[a:a + len(ref)], ref), (rep, i)
+    wr.close()
+
+
 def test_window_plan_covers_c3_law_once():
     """The plan itself at the production scale of one rank's C3 shard (host only)."""
     lens = c3_lengths(2500)
