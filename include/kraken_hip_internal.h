@@ -238,6 +238,10 @@ int krk_ring_select_geometry(uint64_t* digests_per_workgroup, uint64_t* scan_til
  * reads -- the sizes at which the launches of krk_metainfo_serialize_batch_dev and
  * krk_metainfo_parse_sums_batch_dev change shape, for the tests that pin their edges.  No device. */
 int krk_metainfo_json_geometry(uint64_t* serialize_unit_sums, uint64_t* parse_unit_bytes);
+/* The same file's launch geometry: the unit counts one pass of its one-workgroup scan takes (a
+ * 64-bit carry runs between passes), and the workgroups a launch has at the most (with more units,
+ * or more blobs for the parse status, the waves stride).  No device. */
+int krk_metainfo_json_scan_geometry(uint64_t* counts_per_pass, uint64_t* max_workgroups);
 
 /* ------------------------------------------------------- SHA-256 plans
  * Lanes per stream (1, 2 or 8) the library uses for a batch of n_streams streams on

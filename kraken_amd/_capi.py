@@ -125,6 +125,7 @@ def _load() -> C.CDLL:
         "krk_metainfo_serialize_batch_dev": (i, [C.POINTER(krk_metainfo_json_blob), C.c_uint64, vp, vp, vp, vp]),
         "krk_metainfo_parse_sums_batch_dev": (i, [C.POINTER(krk_metainfo_json_span), C.c_uint64, vp, vp, vp, vp]),
         "krk_metainfo_json_geometry": (i, [u64p, u64p]),
+        "krk_metainfo_json_scan_geometry": (i, [u64p, u64p]),
         "krk_sha256_dev": (i, [C.POINTER(vp), u64p, C.c_uint64, vp, vp]),
         "krk_sha256_host": (i, [C.POINTER(vp), u64p, C.c_uint64, u8p]),
         "krk_sha256_dev_on_host": (i, [C.POINTER(vp), u64p, C.c_uint64, i, vp, u8p]),

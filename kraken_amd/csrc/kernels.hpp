@@ -217,6 +217,13 @@ struct alignas(16) MjSerBlob {
     uint8_t name[64];
 };
 static_assert(sizeof(MjSerBlob) == 128, "MjSerBlob layout");
+// The launch geometry of metainfo_json.hip (krk_metainfo_json_scan_geometry reports it).  In mj:
+// piece_bitfield.hip and piece_repiece.hip have a kMaxBlocks of their own.
+namespace mj {
+constexpr uint32_t kMaxBlocks = 1u << 18;  // workgroups a launch has at the most; beyond, the waves stride
+constexpr uint32_t kScanBlock = 256;       // threads of the scan's one workgroup
+constexpr uint32_t kScanPer = 8;           // consecutive counts a thread of the scan takes a pass
+}  // namespace mj
 // scratch: mj_ser_scratch_bytes(n_units) of device memory, 8-byte aligned.  Every byte of every
 // document and every out_len[i] is stored.
 inline uint64_t mj_ser_scratch_bytes(uint64_t n_units) { return 8 * (n_units + 1) + 4 * n_units; }

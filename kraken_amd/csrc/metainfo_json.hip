@@ -32,9 +32,9 @@ namespace krk {
 
 namespace {
 
-constexpr uint32_t kMaxBlocks = 1u << 18;  // beyond: the waves stride
-constexpr uint32_t kScanBlock = 256;
-constexpr uint32_t kScanPer = 8;           // consecutive counts a thread of the scan takes
+using mj::kMaxBlocks;  // kernels.hpp
+using mj::kScanBlock;
+using mj::kScanPer;
 constexpr uint32_t kStageWords = (3 + 64 * mj::kMaxSumBytes + 3) / 4;  // a step's bytes at any phase
 
 // The blob that owns unit u: the last one whose first unit is <= u (piece_repiece.hip).

@@ -121,4 +121,11 @@ int krk_metainfo_json_geometry(uint64_t* serialize_unit_sums, uint64_t* parse_un
     return KRK_OK;
 }
 
+int krk_metainfo_json_scan_geometry(uint64_t* counts_per_pass, uint64_t* max_workgroups) {
+    KRK_CHECK(counts_per_pass && max_workgroups, KRK_EINVAL, "metainfo_json_scan_geometry: null argument");
+    *counts_per_pass = (uint64_t)mj::kScanBlock * mj::kScanPer;
+    *max_workgroups = mj::kMaxBlocks;
+    return KRK_OK;
+}
+
 }  // extern "C"
