@@ -457,16 +457,9 @@ static int chunks_step(Device* D, const krk_chunk* c, uint64_t n, uint32_t* stat
     std::vector<ShaJob> jobs(n);
     CrcBatch items;
     for (uint64_t i = 0; i < n; ++i) {
-        ShaJob& j = jobs[i];
-        j = ShaJob{};
-        j.ptr = reinterpret_cast<uint64_t>(c[i].data);
-        j.len = c[i].length;
-        j.prefix = c[i].offset;
-        j.out = (uint32_t)c[i].blob;
-        j.flags = (c[i].offset + c[i].length == c[i].blob_length ? kShaFinal : 0) | (c[i].offset ? kShaFromState : 0);
-        memcpy(j.h, kIV, sizeof kIV);
+        jobs[i] = chunk_job(c[i].data, c[i].offset, c[i].length, c[i].blob_length, (uint32_t)c[i].blob);
         if (c[i].length)
-            B.add(items, j.ptr, c[i].offset, c[i].offset + c[i].length, c[i].blob_length,
+            B.add(items, jobs[i].ptr, c[i].offset, c[i].offset + c[i].length, c[i].blob_length,
                   (uint64_t)c[i].piece_length, c[i].sums_offset);
     }
     Event fork, j1, j2;

@@ -1,6 +1,6 @@
 // crc_host.cpp -- the C ABI's host-resident CRC-only calls: krk_piece_sums_host with its
-// host / GPU split and NUMA hand-out, the file CRC pass (krk_piece_sums_files) and
-// krk_verify_pieces_host.
+// host / GPU split and NUMA hand-out, krk_piece_sums_files with its host placement, and
+// krk_verify_pieces_host.  Their GPU share goes through the window pass (window_pass.cpp).
 #include <errno.h>
 #include <fcntl.h>
 #include <sys/syscall.h>
@@ -10,94 +10,51 @@
 #include <optional>
 
 #include "offload.hpp"
-#include "runtime.hpp"
-#include "staging.hpp"
+#include "window_pass.hpp"
 
 using namespace krk;
 
-extern "C" {
-
-// The GPU pass of krk_piece_sums_host over host blobs: windows of their bytes go up
-// (pageable bytes through the pinned staging windows; `direct`: the caller's bytes are
-// pinned and DMA'd straight into the device window) and the CRC kernel runs on each.
-static int piece_sums_host_gpu(Device* D, const krk_blob* blobs, uint64_t n_blobs, uint32_t* sums_host,
-                               bool direct) {
-    int r = KRK_OK;
+// The GPU pass of the CRC-only calls: the blobs' bytes packed end to end into windows
+// (PackSched, chunks `place` apart), up on s_a by the way the source allows (window_pass.cpp)
+// and through the CRC kernel on s_b; the sums the blobs cover back to the caller.  The windows
+// are built in the loop (a packed window has few chunks, and krk_piece_sums_host's host
+// threads already fill the CPU budget a build-ahead thread would share; not measured).
+template <class Blob, class Source>
+static int crc_pass(Device* D, const char* what, const Blob* blobs, uint64_t n, Source& src, size_t place,
+                    uint32_t* sums_host) {
     uint64_t lo, hi;
-    sums_span(blobs, n_blobs, &lo, &hi);
+    sums_span(blobs, n, &lo, &hi);
     if (hi == lo) return KRK_OK;
     KRK_CHECK(sums_host, KRK_EINVAL, "sums_host is NULL");
+    KRK_CHECK(n <= 0xFFFFFFFFull, KRK_EINVAL, "more than 2^32 blobs");
+    const size_t W = window_bytes();  // a multiple of 1 MiB
+    KRK_CHECK(W % place == 0, KRK_EINVAL, "%s: window of %zu bytes is no multiple of %zu", what, W, place);
     uint32_t* d_sums = nullptr;
     DevMem mem;
     KRK_HIP(mem.alloc(&d_sums, hi * 4));
     KRK_HIP(hipMemset(d_sums, 0, hi * 4));
-    const size_t W = window_bytes();
-    StagingLease lease;
-    r = lease_staging(D, W, lease);
-    if (r) return r;
-    Pipeline& pl = *lease.p;
-    hipStream_t cp = D->s_a, ks = D->s_b;
-    ItemBuilder B;
-    int k = 0;
-    uint64_t bi = 0, boff = 0;
-    bool gather_ok = direct;  // every blob read at its host address
-    MappedAtHost mapped;
-    for (uint64_t i = 0; gather_ok && i < n_blobs; ++i) gather_ok = mapped(blobs[i].data, blobs[i].length);
-    while (!r && bi < n_blobs) {
-        r = pl.acquire(k);
-        if (r) break;
-        Window& w = pl.w[k];
-        size_t fill = 0;
-        CrcBatch items;
-        std::vector<CopyTask> copies;
-        while (bi < n_blobs && fill < W) {
-            const krk_blob& b = blobs[bi];
-            const uint64_t take = std::min<uint64_t>(b.length - boff, W - fill);
-            if (take) {
-                copies.push_back({w.host + fill, b.data + boff, take});
-                B.add(items, reinterpret_cast<uint64_t>(w.dev + fill), boff, boff + take, b.length,
-                      (uint64_t)b.piece_length, b.sums_offset);
-            }
-            fill += take;
-            boff += take;
-            // keep 16-byte alignment of every run inside the window
-            fill = (fill + 15) & ~size_t(15);
-            if (boff >= b.length) { ++bi; boff = 0; }
-        }
-        // pinned bytes go up straight from the caller's pages: a DMA a copy in windows of few
-        // copies (many small DMAs cost more than the staging copy, staging.hpp
-        // kDirectMaxCalls), else one gather launch that reads them over PCIe (gather.hip)
-        const bool dw = direct && copies.size() <= kDirectMaxCalls;
-        const bool gw = direct && !dw && gather_ok;
-        hipError_t up = hipSuccess;
-        if (dw || gw)
-            for (CopyTask& c : copies) c.dst = w.dev + (c.dst - w.host);
-        if (gw) {
-            std::vector<GatherSpan> spans;
-            spans.reserve(copies.size());
-            for (const CopyTask& c : copies) spans.push_back({c.dst, c.src, c.n});
-            r = pl.h2d_gather(D, k, spans, cp);
-            if (r) break;
-        } else {
-            up = dw ? pl.h2d_direct(k, copies, cp) : (par_copy(copies), pl.h2d(k, std::min(fill, W), cp));
-        }
-        if (up != hipSuccess || hipStreamWaitEvent(ks, w.copied, 0) != hipSuccess) {
-            set_error(KRK_EHIP, "piece_sums_host: staging copy failed");
-            r = KRK_EHIP;
-            break;
-        }
-        r = run_items(D, items, d_sums, ks);
-        if (r) break;
-        pl.release(k, 0, ks);
-        k = pl.next(k);
+    std::vector<uint64_t> lens(n), soff(n);
+    std::vector<int64_t> plens(n);
+    for (uint64_t i = 0; i < n; ++i) {
+        lens[i] = blobs[i].length;
+        plens[i] = blobs[i].piece_length;
+        soff[i] = blobs[i].sums_offset;
     }
-    if (!r && hipStreamSynchronize(ks) != hipSuccess) { set_error(KRK_EHIP, "sync failed"); r = KRK_EHIP; }
+    PackSched sched(lens.data(), n, W, place);
+    const WindowPass pass{what, D, [&](std::vector<WinChunk>& w) { return sched.next(w); }, place, W, D->s_a, nullptr,
+                          D->s_b, lens.data(), plens.data(), soff.data(), nullptr, nullptr, d_sums, /*build_ahead=*/0,
+                          nullptr};
+    int r = run_windows(pass, src);
+    // drain what was queued even after a read error (the windows' kernels read the buffers)
+    if (hipStreamSynchronize(D->s_b) != hipSuccess && !r) { set_error(KRK_EHIP, "sync failed"); r = KRK_EHIP; }
     if (!r && hipMemcpy(sums_host + lo, d_sums + lo, (hi - lo) * 4, hipMemcpyDeviceToHost) != hipSuccess) {
         set_error(KRK_EHIP, "sums copy-out failed");
         r = KRK_EHIP;
     }
     return r;
 }
+
+extern "C" {
 
 // krk_piece_sums_host / krk_verify_pieces_host: the reference hashes each received
 // piece on the host (lib/torrent/storage/agentstorage/torrent.go:182-193), and one host
@@ -391,7 +348,11 @@ int krk_piece_sums_host(const krk_blob* blobs, uint64_t n_blobs, uint32_t* sums_
     double gpu_s = 0;
     if (!gpu.empty()) {
         std::vector<uint32_t> gs(g_sums);
-        r = piece_sums_host_gpu(D, gpu.data(), gpu.size(), gs.data(), all_pinned);
+        // pinned bytes go up straight from the caller's pages (a DMA a chunk or the gather),
+        // pageable ones through the pinned staging windows
+        MemSource src(gpu.data(), gpu.size());
+        src.setup({}, all_pinned, /*gather_mode=*/-1, D->s_a);
+        r = crc_pass(D, "piece_sums_host", gpu.data(), gpu.size(), src, 16, gs.data());
         gpu_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         if (!r)
             for (size_t j = 0; j < gpu.size(); ++j) {
@@ -505,17 +466,13 @@ static int piece_sums_files_host(const krk_file_blob* files, uint64_t n, uint32_
 int krk_piece_sums_files(const krk_file_blob* files, uint64_t n, uint32_t* sums_host) {
     if (!n) return KRK_OK;
     KRK_CHECK(files, KRK_EINVAL, "files is NULL");
-    uint64_t lo = ~0ull, hi = 0, bytes = 0;
+    uint64_t lo, hi, bytes = 0;
     for (uint64_t i = 0; i < n; ++i) {
         KRK_CHECK(files[i].path, KRK_EINVAL, "file %llu: path is NULL", (unsigned long long)i);
         KRK_CHECK(files[i].piece_length > 0, KRK_EINVAL, "piece length must be positive");
-        const uint64_t np = krk_num_pieces(files[i].length, files[i].piece_length);
         bytes += files[i].length;
-        if (np) {
-            lo = std::min(lo, files[i].sums_offset);
-            hi = std::max(hi, files[i].sums_offset + np);
-        }
     }
+    sums_span(files, n, &lo, &hi);
     // An empty file has no piece to read, but Generate opens it (GetCacheFileReader,
     // lib/metainfogen/generator.go:47-49): a missing or unreadable one fails.
     for (uint64_t i = 0; i < n; ++i)
@@ -535,98 +492,9 @@ int krk_piece_sums_files(const krk_file_blob* files, uint64_t n, uint32_t* sums_
     if (where != KRK_PLACE_GPU) return piece_sums_files_host(files, n, sums_host);
     KRK_DEVICE(D);
     const bool want_direct = KRK_OP_ENV("KRK_FILE_DIRECT") && atoi(KRK_OP_ENV("KRK_FILE_DIRECT")) > 0;
-    uint32_t* d_sums = nullptr;
-    DevMem mem;
-    KRK_HIP(mem.alloc(&d_sums, hi * 4));
-    KRK_HIP(hipMemset(d_sums, 0, hi * 4));
-    const size_t W = window_bytes();  // a multiple of 1 MiB
-    StagingLease lease;
-    int r = lease_staging(D, W, lease);
-    Pipeline* pl = lease.p;
-    hipStream_t cp = D->s_a, ks = D->s_b;
-    ItemBuilder B;
-    std::vector<int> fds(n, -1);
-    std::vector<char> direct(n, 0);
-    auto open_file = [&](uint64_t i) -> int {
-        if (fds[i] >= 0) return KRK_OK;
-        int fd = -1;
-        if (want_direct) {
-            fd = open(files[i].path, O_RDONLY | O_DIRECT | O_CLOEXEC);
-            direct[i] = fd >= 0;
-        }
-        if (fd < 0) fd = open(files[i].path, O_RDONLY | O_CLOEXEC);
-        if (fd < 0) {
-            set_error(KRK_EIO, "open %s: %s", files[i].path, strerror(errno));
-            return KRK_EIO;
-        }
-        fds[i] = fd;
-        return KRK_OK;
-    };
-    int k = 0;
-    uint64_t bi = 0, boff = 0;
-    while (!r && bi < n) {
-        r = pl->acquire(k);
-        if (r) break;
-        Window& w = pl->w[k];
-        size_t fill = 0;
-        CrcBatch items;
-        std::vector<ReadTask> plain, odirect;
-        std::vector<uint64_t> finished;
-        while (bi < n && fill < W) {
-            const krk_file_blob& f = files[bi];
-            const uint64_t take = std::min<uint64_t>(f.length - boff, W - fill);
-            if (take) {
-                r = open_file(bi);
-                if (r) break;
-                (direct[bi] ? odirect : plain).push_back({fds[bi], boff, w.host + fill, (size_t)take, (size_t)bi});
-                B.add(items, reinterpret_cast<uint64_t>(w.dev + fill), boff, boff + take, f.length,
-                      (uint64_t)f.piece_length, f.sums_offset);
-            }
-            fill += take;
-            boff += take;
-            fill = (fill + 4095) & ~size_t(4095);  // every file starts page-aligned in the window
-            if (boff >= f.length) {
-                finished.push_back(bi);
-                ++bi;
-                boff = 0;
-            }
-        }
-        if (r) break;
-        for (int pass = 0; pass < 2 && !r; ++pass) {
-            const auto& tasks = pass ? odirect : plain;
-            if (tasks.empty()) continue;
-            int e = 0;
-            const long bad = par_read(tasks, pass == 1, &e);
-            if (bad >= 0) {
-                const char* path = files[tasks[bad].blob].path;
-                if (e) set_error(KRK_EIO, "read blob: %s: %s", path, strerror(e));
-                else set_error(KRK_EIO, "read blob: %s: unexpected EOF", path);
-                r = KRK_EIO;
-            }
-        }
-        for (uint64_t i : finished) {
-            if (fds[i] >= 0) close(fds[i]);
-            fds[i] = -1;
-        }
-        if (r) break;
-        if (pl->h2d(k, std::min(fill, W), cp) != hipSuccess || hipStreamWaitEvent(ks, w.copied, 0) != hipSuccess) {
-            set_error(KRK_EHIP, "piece_sums_files: staging copy failed");
-            r = KRK_EHIP;
-            break;
-        }
-        r = run_items(D, items, d_sums, ks);
-        if (r) break;
-        pl->release(k, 0, ks);
-        k = pl->next(k);
-    }
-    for (int fd : fds)
-        if (fd >= 0) close(fd);
-    if (hipStreamSynchronize(ks) != hipSuccess && !r) { set_error(KRK_EHIP, "sync failed"); r = KRK_EHIP; }
-    if (!r && hipMemcpy(sums_host + lo, d_sums + lo, (hi - lo) * 4, hipMemcpyDeviceToHost) != hipSuccess) {
-        set_error(KRK_EHIP, "sums copy-out failed");
-        r = KRK_EHIP;
-    }
-    return r;
+    // every read by par_read; every file starts page-aligned in the window (O_DIRECT)
+    FileSource src(files, n, want_direct, /*async=*/false);
+    return crc_pass(D, "piece_sums_files", files, n, src, 4096, sums_host);
 }
 
 int krk_verify_pieces_host(const uint8_t* const* data, const uint64_t* lengths, const uint32_t* expected,

@@ -159,15 +159,9 @@ int launch_sha(Engine* E, Inflight* f) {
     uint32_t lo = UINT32_MAX, hi = 0;
     for (size_t i = 0; i < n; ++i) {
         Req* r = f->batch[i];
-        ShaJob& j = jobs[i];
-        j = ShaJob{};
         // zero-copy: the producer waves load the pinned slot over PCIe (Kind, engine.hpp)
-        j.ptr = reinterpret_cast<uint64_t>(r->slot ? r->slot->mapped : reinterpret_cast<const uint8_t*>(E->d_state));
-        j.len = r->len;
-        j.prefix = r->prefix;
-        j.out = r->row;
-        j.flags = (r->final ? kShaFinal : 0) | (r->prefix ? kShaFromState : 0);
-        memcpy(j.h, kIV, 32);
+        jobs[i] = sha_job(r->slot ? r->slot->mapped : reinterpret_cast<const uint8_t*>(E->d_state), r->prefix, r->len,
+                          r->final, r->row);
         f->max_len = std::max<uint64_t>(f->max_len, r->len);
         if (r->final) lo = std::min(lo, r->row), hi = std::max(hi, r->row);
     }

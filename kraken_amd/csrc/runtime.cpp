@@ -1,7 +1,7 @@
 // runtime.cpp -- the C ABI (include/kraken_hip.h): error state, device contexts and their
 // teardown, synthetic fills, the memory / stream / event wrappers, timing and stats.  The
 // batch calls live in batch_dev.cpp (device-resident), crc_host.cpp (host-resident CRC),
-// windows.cpp (host-resident digest + metainfo) and placement.cpp (HRW, ring).
+// windows.cpp (host-resident digest + metainfo; the pass itself in window_pass.cpp) and placement.cpp (HRW, ring).
 #include <errno.h>
 #include <hip/hip_runtime.h>
 #include <stdarg.h>

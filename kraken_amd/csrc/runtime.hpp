@@ -1,6 +1,6 @@
 // runtime.hpp -- internal to libkraken_hip: device contexts, the stream-ordered
 // scratch cache, the CRC work builder and the SHA job runner shared by the C ABI
-// (runtime.cpp, batch_dev.cpp, info_hash_dev.cpp, crc_host.cpp, placement.cpp, ring_select_abi.cpp, windows.cpp) and the
+// (runtime.cpp, batch_dev.cpp, info_hash_dev.cpp, crc_host.cpp, placement.cpp, ring_select_abi.cpp, window_pass.cpp, windows.cpp) and the
 // submission engine (engine.hpp, engine.cpp).  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -693,16 +693,23 @@ inline int run_gather(Device* D, const std::vector<GatherSpan>& spans, hipStream
     return KRK_OK;
 }
 
-inline ShaJob full_job(const void* p, uint64_t len, uint32_t out) {
+// The SHA-256 job of bytes [off, off + len) of a stream, at p: chained from the stream's
+// state row `out` unless it starts the stream, padded and written out as the digest if final.
+inline ShaJob sha_job(const void* p, uint64_t off, uint64_t len, bool final, uint32_t out) {
     ShaJob j{};
     j.ptr = reinterpret_cast<uint64_t>(p);
     j.len = len;
-    j.prefix = 0;
+    j.prefix = off;
     j.out = out;
-    j.flags = kShaFinal;
+    j.flags = (final ? kShaFinal : 0) | (off ? kShaFromState : 0);
     memcpy(j.h, kIV, sizeof kIV);
     return j;
 }
+// ... final when the chunk ends its blob of blob_len bytes
+inline ShaJob chunk_job(const void* p, uint64_t off, uint64_t len, uint64_t blob_len, uint32_t out) {
+    return sha_job(p, off, len, off + len == blob_len, out);
+}
+inline ShaJob full_job(const void* p, uint64_t len, uint32_t out) { return sha_job(p, 0, len, true, out); }
 
 // Host CPUs this process may use (host_pool.cpp): KRK_HOST_CPUS, else the node's CPUs
 // (affinity capped by the cgroup quota) / LOCAL_WORLD_SIZE under a launcher, else the

@@ -41,10 +41,9 @@ struct Window {
     uint8_t* host = nullptr;
     uint8_t* dev = nullptr;
     size_t cap = 0;
-    hipEvent_t copied = nullptr;    // the H2D out of `host` has finished: host buffer reusable
-    hipEvent_t consumed = nullptr;  // single-stream users: all work reading `dev` has finished
+    hipEvent_t copied = nullptr;  // the H2D out of `host` has finished: host buffer reusable
     hipEvent_t done[2] = {nullptr, nullptr};  // kernels reading `dev`, one event per kernel stream
-    bool inflight = false, copying = false;
+    bool copying = false;
     bool done_pending[2] = {false, false};
 };
 
@@ -58,11 +57,7 @@ constexpr size_t kDirectMaxCalls = 64;
 // refilled once its H2D is done; the H2D into its device side waits (on the copy
 // stream only) for the kernels that read the previous contents, so the upload of
 // window k+1 overlaps the kernels of window k.
-struct CopyTask {
-    uint8_t* dst;
-    const uint8_t* src;
-    size_t n;
-};
+using CopyTask = GatherSpan;  // {dst, src, n}: a host copy, a DMA or a gather span alike
 
 // KRK_STAGING_WINDOWS (2..4, default 3): windows in the ring; with more, a window's host copy
 // or file reads may run further ahead of the upload and kernels of the earlier ones.  C2's
@@ -84,14 +79,12 @@ struct Pipeline {
     int next(int k) const { return (k + 1) % n; }
     ~Pipeline() {
         for (auto& x : w) {
-            if (x.inflight) hipEventSynchronize(x.consumed);
             if (x.copying) hipEventSynchronize(x.copied);
             for (int i = 0; i < 2; ++i)
                 if (x.done_pending[i]) hipEventSynchronize(x.done[i]);
             if (x.host) hipHostFree(x.host);
             if (x.dev) hipFree(x.dev);
             if (x.copied) hipEventDestroy(x.copied);
-            if (x.consumed) hipEventDestroy(x.consumed);
             for (auto e : x.done)
                 if (e) hipEventDestroy(e);
         }
@@ -104,75 +97,61 @@ struct Pipeline {
             KRK_HIP(hipHostMalloc(reinterpret_cast<void**>(&x.host), cap, hipHostMallocDefault));
             KRK_HIP(hipMalloc(reinterpret_cast<void**>(&x.dev), cap));
             KRK_HIP(hipEventCreateWithFlags(&x.copied, hipEventDisableTiming));
-            KRK_HIP(hipEventCreateWithFlags(&x.consumed, hipEventDisableTiming));
             for (auto& e : x.done) KRK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         }
         return KRK_OK;
     }
     // Host side of window k is free for refilling.
     int acquire(int k) {
-        if (w[k].inflight) {
-            KRK_HIP(hipEventSynchronize(w[k].consumed));
-            w[k].inflight = false;
-        }
         if (w[k].copying) {
             KRK_HIP(hipEventSynchronize(w[k].copied));
             w[k].copying = false;
         }
         return KRK_OK;
     }
-    // Upload n bytes of window k on cp, after the kernels that read its last contents.
+    // The three ways up into device window k on cp, each after the kernels that read its last
+    // contents and each recording `copied`: n bytes of the pinned host window; the caller's
+    // pinned bytes, a DMA a task; the caller's page-locked bytes by ONE gather launch
+    // (gather.hip).  tasks' and spans' dst are device addresses in the window.
     hipError_t h2d(int k, size_t n, hipStream_t cp) {
-        Window& x = w[k];
-        for (int i = 0; i < 2; ++i)
-            if (x.done_pending[i]) {
-                hipError_t e = hipStreamWaitEvent(cp, x.done[i], 0);
-                if (e != hipSuccess) return e;
-                x.done_pending[i] = false;
-            }
-        hipError_t e = hipMemcpyAsync(x.dev, x.host, n, hipMemcpyHostToDevice, cp);
-        if (e == hipSuccess) e = hipEventRecord(x.copied, cp);
-        if (e == hipSuccess) x.copying = true;
-        return e;
+        hipError_t e = wait_readers(w[k], cp);
+        if (e == hipSuccess) e = hipMemcpyAsync(w[k].dev, w[k].host, n, hipMemcpyHostToDevice, cp);
+        return e == hipSuccess ? mark_copied(w[k], cp) : e;
     }
-    // The caller's pinned bytes DMA'd straight into device window k (tasks' dst are
-    // device addresses in it), after the kernels that read its last contents.
     hipError_t h2d_direct(int k, const std::vector<CopyTask>& tasks, hipStream_t cp) {
-        Window& x = w[k];
-        for (int i = 0; i < 2; ++i)
-            if (x.done_pending[i]) {
-                hipError_t e = hipStreamWaitEvent(cp, x.done[i], 0);
-                if (e != hipSuccess) return e;
-                x.done_pending[i] = false;
-            }
-        for (const auto& t : tasks) {
-            hipError_t e = hipMemcpyAsync(t.dst, t.src, t.n, hipMemcpyHostToDevice, cp);
-            if (e != hipSuccess) return e;
-        }
-        hipError_t e = hipEventRecord(x.copied, cp);
-        if (e == hipSuccess) x.copying = true;
-        return e;
+        hipError_t e = wait_readers(w[k], cp);
+        for (size_t i = 0; e == hipSuccess && i < tasks.size(); ++i)
+            e = hipMemcpyAsync(tasks[i].dst, tasks[i].src, tasks[i].n, hipMemcpyHostToDevice, cp);
+        return e == hipSuccess ? mark_copied(w[k], cp) : e;
     }
-    // The caller's page-locked bytes gathered into device window k by ONE gather launch on
-    // cp (spans' dst are device addresses in it), after the kernels that read its last
-    // contents.
     int h2d_gather(Device* D, int k, const std::vector<GatherSpan>& spans, hipStream_t cp) {
-        Window& x = w[k];
-        for (int i = 0; i < 2; ++i)
-            if (x.done_pending[i]) {
-                KRK_HIP(hipStreamWaitEvent(cp, x.done[i], 0));
-                x.done_pending[i] = false;
-            }
+        KRK_HIP(wait_readers(w[k], cp));
         const int r = run_gather(D, spans, cp);
         if (r) return r;
-        KRK_HIP(hipEventRecord(x.copied, cp));
-        x.copying = true;
+        KRK_HIP(mark_copied(w[k], cp));
         return KRK_OK;
     }
     // Kernel stream ks (slot 0 or 1) has enqueued everything that reads window k.
     hipError_t release(int k, int slot, hipStream_t ks) {
         hipError_t e = hipEventRecord(w[k].done[slot], ks);
         if (e == hipSuccess) w[k].done_pending[slot] = true;
+        return e;
+    }
+
+  private:
+    // cp waits for the kernels that last read the slot
+    static hipError_t wait_readers(Window& x, hipStream_t cp) {
+        for (int i = 0; i < 2; ++i)
+            if (x.done_pending[i]) {
+                const hipError_t e = hipStreamWaitEvent(cp, x.done[i], 0);
+                if (e != hipSuccess) return e;
+                x.done_pending[i] = false;
+            }
+        return hipSuccess;
+    }
+    static hipError_t mark_copied(Window& x, hipStream_t cp) {
+        const hipError_t e = hipEventRecord(x.copied, cp);
+        if (e == hipSuccess) x.copying = true;
         return e;
     }
 };

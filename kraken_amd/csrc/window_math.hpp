@@ -1,7 +1,8 @@
 // window_math.hpp -- the arithmetic of the host-resident window passes, free of any runtime:
-// the window schedule (which bytes of which blob a window carries, windows.cpp) and the cut of
-// a window's fill into per-thread spans (par_copy / par_read, staging.hpp).  Included by the
-// library and by tests/native/window_math_main.cpp, which checks both against a byte walk.
+// the two schedules (which bytes of which blob a window carries: WindowSched for the digest
+// calls, PackSched for the CRC-only ones; run by window_pass.cpp) and the cut of a window's
+// fill into per-thread spans (par_copy / par_read, staging.hpp).  Included by the library and
+// by tests/native/window_math_main.cpp, which checks all three against a byte walk.
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -75,6 +76,34 @@ class WindowSched {
     uint64_t max_live_ = 0;
     uint64_t max_chunk_ = UINT64_MAX;
 };
+
+// The packing schedule of the CRC-only passes: blobs in index order, a portion of
+// min(rest of the blob, W - fill), `fill` rounded up to `place` after every portion; a window
+// ends at fill >= W or with the last blob, and a zero-length blob yields no chunk.
+// Precondition: W % place == 0 (W - fill wraps otherwise).
+class PackSched {
+  public:
+    PackSched(const uint64_t* lens, uint64_t n, uint64_t W, uint64_t place) : L_(lens), n_(n), W_(W), place_(place) {}
+    // The next window's chunks; false once every byte has been handed out.
+    bool next(std::vector<WinChunk>& out) {
+        out.clear();
+        for (uint64_t fill = 0; b_ < n_ && fill < W_;) {
+            const uint64_t take = std::min(L_[b_] - off_, W_ - fill);
+            if (take) out.push_back({(uint32_t)b_, off_, take});
+            off_ += take;
+            fill = (fill + take + place_ - 1) / place_ * place_;
+            if (off_ >= L_[b_]) ++b_, off_ = 0;
+        }
+        return !out.empty();
+    }
+
+  private:
+    const uint64_t* L_;
+    uint64_t n_, W_, place_, b_ = 0, off_ = 0;
+};
+
+// Both schedules place a window's chunks by one rule, which the pass applies (window_pass.cpp):
+// chunk k + 1 starts at pos_k + round_up(len_k, place).
 
 // ------------------------------------------------------------- a window's fill, cut in spans
 // A window's fill tasks laid end to end form one byte stream, cut into spans that threads

@@ -1,37 +1,26 @@
-// windows.cpp -- host-resident batches through the pinned staging windows:
-// the upload / cache-fill verify of origin/blobserver/uploader.go:74-94 and
-// lib/store/ca_store.go:99-135 (Digester over the bytes) fused with the metainfo of
-// lib/metainfogen/generator.go:41-58 (piece CRCs of the same bytes), so each byte is read
-// once -- from the caller's buffers (krk_metainfo_digest_host) or from the cache files
-// themselves (krk_metainfo_digest_files) -- and crosses PCIe once, where the reference
-// reads every upload twice.
+// windows.cpp -- the C ABI's host-resident digest calls: the upload /
+// cache-fill verify of origin/blobserver/uploader.go:74-94 and lib/store/ca_store.go:99-135
+// (Digester over the bytes) fused with the metainfo of lib/metainfogen/generator.go:41-58
+// (piece CRCs of the same bytes), so each byte is read once -- from the caller's buffers
+// (krk_metainfo_digest_host) or from the cache files themselves (krk_metainfo_digest_files) --
+// and crosses PCIe once, where the reference reads every upload twice.  Also here: the window
+// schedule's C ABI, the krk_windows_last_* statistics and the gather's test entry point.  The
+// pass itself is window_pass.cpp.
 //
-// The window schedule (the C3 machinery of kraken_amd/windowed.py, here in C++): every live
-// blob advances by the same chunk per window (about W bytes a window), SHA-256 chained
-// through per-blob midstates in HBM and the chunk's piece CRCs XOR-accumulated into its
-// pieces (CRC-32 is linear, so any cut is legal).  At most `cap` blobs are live, admitted
-// longest first so the longest chain starts in window 0: by default 7/8 of the largest
-// stream count the SHA-256 launch plan still runs on two lanes a stream (14,336 on 256
-// CUs), which keeps every window on a multi-lane plan and leaves an eighth of the CUs free
-// of SHA workgroups for the window's CRC launch, queued beside it on another stream
-// (profiles/r02/c3_live_cap.jsonl).  The host's work per window is O(live).
-#include <dirent.h>
+// The window schedule (the C3 machinery of kraken_amd/windowed.py, here in C++: WindowSched,
+// window_math.hpp): at most `cap` blobs are live, admitted longest first so the longest chain
+// starts in window 0: by default 7/8 of the largest stream count the SHA-256 launch plan still
+// runs on two lanes a stream (14,336 on 256 CUs), which keeps every window on a multi-lane
+// plan and leaves an eighth of the CUs free of SHA workgroups for the window's CRC launch,
+// queued beside it on another stream (profiles/r02/c3_live_cap.jsonl).
 #include <sys/mman.h>
-#include <sys/resource.h>
 
-#include <condition_variable>
-#include <deque>
 #include <thread>
 
-#include "host_register.hpp"
 #include "offload.hpp"
-#include "runtime.hpp"
-#include "staging.hpp"
-#include "window_math.hpp"
+#include "window_pass.hpp"
 
 namespace krk {
-
-// The window schedule itself (WindowSched) is in window_math.hpp.
 
 // Live streams per window on device D: 7/8 of the largest stream count whose SHA-256 launch
 // still runs two (or eight) lanes a stream, a multiple of the two-pair workgroup's 64.
@@ -47,403 +36,7 @@ uint64_t window_stream_cap(Device* D) {
 }
 
 namespace {
-
-// Where a window's bytes come from: the caller's buffers or the cache files.
-struct Filler {
-    virtual ~Filler() = default;
-    // bytes [off, off + len) of blob b into dst (host, pinned); the whole window at once
-    struct Task {
-        uint32_t b;
-        uint64_t off, len;
-        uint8_t* dst;
-    };
-    virtual int fill(const std::vector<Task>& tasks) = 0;
-    // The source is page-locked: its chunks can be DMA'd straight into the device window.
-    virtual const uint8_t* pinned_src(uint32_t /*blob*/, uint64_t /*off*/) const { return nullptr; }
-    virtual bool pinned_all() const { return false; }
-    // ... and the GPU addresses it at the host address (the gather reads it there)
-    virtual bool pinned_mapped() const { return false; }
-    // The caller's pageable bytes made page-locked for the gather (host_register.hpp), or null.
-    virtual HostRegistry* registry() { return nullptr; }
-    virtual const uint8_t* src(uint32_t /*blob*/, uint64_t /*off*/) const { return nullptr; }
-};
-
-struct MemFiller : Filler {
-    const krk_blob* blobs;
-    bool pinned = false;  // every windowed blob page-locked (krk_host_alloc): no staging copy
-    bool mapped = false;  // ... at device addresses equal to the host ones
-    std::unique_ptr<HostRegistry> reg;  // pageable blobs registered for the gather
-    hipStream_t gather_stream = nullptr;  // where the gathers ran (drained before unregistering)
-    explicit MemFiller(const krk_blob* b) : blobs(b) {}
-    ~MemFiller() override {
-        if (reg) reg->finish(gather_stream);
-    }
-    const uint8_t* pinned_src(uint32_t b, uint64_t off) const override { return pinned ? blobs[b].data + off : nullptr; }
-    bool pinned_all() const override { return pinned; }
-    bool pinned_mapped() const override { return mapped; }
-    HostRegistry* registry() override { return reg.get(); }
-    const uint8_t* src(uint32_t b, uint64_t off) const override { return blobs[b].data + off; }
-    int fill(const std::vector<Task>& tasks) override {
-        std::vector<CopyTask> c;
-        c.reserve(tasks.size());
-        for (const Task& t : tasks)
-            if (t.len) c.push_back({t.dst, blobs[t.b].data + t.off, (size_t)t.len});
-        par_copy(c);
-        return KRK_OK;
-    }
-};
-
-// A blob's file is opened at its first chunk and closed after its last; live blobs <= the
-// descriptor budget (the window cap is capped by it), so no descriptor is reopened.
-struct FileFiller : Filler {
-    const krk_file_blob* files;
-    bool direct;
-    std::vector<int> fd;
-    std::vector<char> is_direct;
-    std::unique_ptr<std::atomic<uint64_t>[]> ra;  // each file's readahead mark (par_read)
-    AioReader aio;                                  // the O_DIRECT chunks of a window
-    FileFiller(const krk_file_blob* f, uint64_t n, bool want_direct)
-        : files(f), direct(want_direct), fd(n, -1), is_direct(n, 0), ra(new std::atomic<uint64_t>[n]()) {}
-    ~FileFiller() override {
-        for (int x : fd)
-            if (x >= 0) close(x);
-    }
-    int open_file(uint32_t i) {
-        if (fd[i] >= 0) return KRK_OK;
-        int x = -1;
-        if (direct) {
-            x = open(files[i].path, O_RDONLY | O_DIRECT | O_CLOEXEC);
-            is_direct[i] = x >= 0;
-        }
-        if (x < 0) x = open(files[i].path, O_RDONLY | O_CLOEXEC);
-        KRK_CHECK(x >= 0, KRK_EIO, "open %s: %s", files[i].path, strerror(errno));
-        fd[i] = x;
-        return KRK_OK;
-    }
-    int fill(const std::vector<Task>& tasks) override {
-        std::vector<ReadTask> plain, odirect;
-        for (const Task& t : tasks) {
-            // every file is opened, an empty one too: Generate / verify open the file and
-            // fail on a missing one
-            int r = open_file(t.b);
-            if (r) return r;
-            if (!t.len) continue;
-            (is_direct[t.b] ? odirect : plain)
-                .push_back({fd[t.b], t.off, t.dst, (size_t)t.len, (size_t)t.b, &ra[t.b], files[t.b].length});
-        }
-        for (int pass = 0; pass < 2; ++pass) {
-            const auto& rt = pass ? odirect : plain;
-            if (rt.empty()) continue;
-            int e = 0;
-            long bad = pass == 1 && use_aio() ? aio.read(rt, &e) : -2;
-            if (bad == -2) bad = par_read(rt, pass == 1, &e);
-            if (bad >= 0) {
-                const char* path = files[rt[bad].blob].path;
-                if (e) set_error(KRK_EIO, "read blob: %s: %s", path, strerror(e));
-                else set_error(KRK_EIO, "read blob: %s: unexpected EOF", path);
-                return KRK_EIO;
-            }
-        }
-        for (const Task& t : tasks)  // a blob's last chunk: its file is done
-            if (t.off + t.len == files[t.b].length && fd[t.b] >= 0) {
-                close(fd[t.b]);
-                fd[t.b] = -1;
-            }
-        return KRK_OK;
-    }
-};
-
-// File descriptors the file batches may hold open, shared by the whole process (ADVICE r04:
-// every *_multi worker and every concurrent caller took the whole remaining budget for
-// itself): the soft RLIMIT_NOFILE less the descriptors open at first use and a reserve for
-// the rest of the process, handed out in leases.  A call waits only while every descriptor
-// is leased, and then takes at least one.
-class FdPool {
-  public:
-    uint64_t acquire(uint64_t want) {
-        std::unique_lock<std::mutex> g(mu_);
-        if (!init_) {
-            free_ = total_ = initial_budget();
-            init_ = true;
-        }
-        cv_.wait(g, [&] { return free_ > 0; });
-        const uint64_t take = std::max<uint64_t>(1, std::min(want, free_));
-        free_ -= take;
-        return take;
-    }
-    void release(uint64_t n) {
-        {
-            std::lock_guard<std::mutex> g(mu_);
-            free_ += n;
-        }
-        cv_.notify_all();
-    }
-    uint64_t total() {
-        std::lock_guard<std::mutex> g(mu_);
-        return init_ ? total_ : initial_budget();
-    }
-
-  private:
-    static uint64_t initial_budget() {
-        if (const char* e = KRK_OP_ENV("KRK_FD_BUDGET"))  // tests: a small budget without touching the rlimit
-            if (strtoull(e, nullptr, 10) > 0) return strtoull(e, nullptr, 10);
-        struct rlimit rl {};
-        if (getrlimit(RLIMIT_NOFILE, &rl) != 0 || rl.rlim_cur == RLIM_INFINITY) return uint64_t(1) << 20;
-        uint64_t open_now = 0;
-        if (DIR* d = opendir("/proc/self/fd")) {
-            while (readdir(d)) ++open_now;
-            closedir(d);
-        }
-        const uint64_t reserve = 64 + open_now;
-        return rl.rlim_cur > reserve + 16 ? rl.rlim_cur - reserve : 16;
-    }
-    std::mutex mu_;
-    std::condition_variable cv_;
-    bool init_ = false;
-    uint64_t free_ = 0, total_ = 0;
-};
-FdPool& fd_pool() {
-    static FdPool* p = new FdPool();  // leaked: used until exit
-    return *p;
-}
-struct FdLease {
-    uint64_t n;
-    explicit FdLease(uint64_t want) : n(fd_pool().acquire(want)) {}
-    ~FdLease() { fd_pool().release(n); }
-    FdLease(const FdLease&) = delete;
-    FdLease& operator=(const FdLease&) = delete;
-};
-
-struct CallStats {
-    uint64_t max_live = 0;
-    int windows = 0;
-    int direct_windows = 0;  // windows DMA'd straight from the caller's page-locked memory
-    int gather_windows = 0;  // windows gathered by the GPU from page-locked / registered caller memory
-    uint64_t host_blobs = 0;
-    uint64_t registered_bytes = 0;  // caller bytes registered for the gather
-    double register_s = 0;          // helper-thread seconds spent registering them
-    // the window loop's wall seconds and where it waited: for a free window (acquire), filling
-    // windows from the source (fill: staging copies or file reads), enqueueing copies + kernels
-    double loop_s = 0, acquire_s = 0, fill_s = 0, enqueue_s = 0;
-    double resident = -1;  // file batches: the page-cache resident share of the sampled files
-    bool direct_reads = false;  // file batches: read with O_DIRECT
-    uint64_t live_at_copyout = 0;  // registry segments still registered when the results were copied out
-};
-thread_local CallStats t_last_call;
-
-
-// The windows of one host-resident batch: the blobs not in `skip`, chunk by chunk, into the
-// device's staging windows and through both kernels.  d_sums / d_dig / d_state indexed like
-// the caller's blobs (sums by sums_off).  Asynchronous on the device's streams; returns once
-// the last window is queued (the caller synchronises s_main / s_a / s_b).
-int windows_pass(Device* D, uint64_t n, const uint64_t* lens, const int64_t* plens, const uint64_t* soff,
-                 const std::vector<char>& skip, Filler& filler, uint64_t align, uint64_t cap, uint32_t* d_sums,
-                 uint8_t* d_dig, uint32_t* d_state, CallStats* st, bool crc = true) {
-    std::vector<uint32_t> blobs;
-    for (uint64_t i = 0; i < n; ++i)
-        if (!skip[i]) blobs.push_back((uint32_t)i);
-    st->max_live = 0;
-    st->windows = st->direct_windows = st->gather_windows = 0;
-    st->loop_s = st->acquire_s = st->fill_s = st->enqueue_s = 0;
-    st->direct_reads = false;
-    if (blobs.empty()) return KRK_OK;
-    const size_t W = window_bytes();
-    const uint64_t live_cap = std::min<uint64_t>(cap, blobs.size());
-    WindowSched sched(lens, blobs, W, live_cap, align);
-    const size_t place = std::max<uint64_t>(align == 64 ? 16 : align, 16);  // chunk start alignment in the window
-    // a window holds about W bytes, but never less than one minimum chunk (the schedule's
-    // alignment) a live blob, each rounded up to `place` (a small KRK_WINDOW_MB
-    // or a large KRK_LIVE_CAP made live x 64 > W + 16 x live)
-    const uint64_t span = std::max<uint64_t>(W, live_cap * std::max<uint64_t>(align, 64)) + place * live_cap;
-    StagingLease lease;
-    int r = lease_staging(D, span, lease);
-    if (r) return r;
-    Pipeline& pl = *lease.p;
-    hipStream_t cp = D->s_main, ks = D->s_a, kc = D->s_b;
-    std::vector<WinChunk> win;
-    // the gather (gather.hip): page-locked caller memory goes up in one launch a window, read
-    // by the GPU -- pinned blobs as they are, pageable ones once the registry has registered
-    // the pages the window reads (a dry run of the same schedule tells it which, when)
-    HostRegistry* reg = filler.registry();
-    if (reg) {
-        WindowSched dry(lens, blobs, W, live_cap, align);
-        for (int w = 0; dry.next(win); ++w)
-            for (const WinChunk& c : win) reg->need(w, filler.src(c.blob, c.off), c.len);
-        reg->start(std::min(4, std::max(1, host_threads_for_call() / 4)));
-    }
-    bool gather_ok = reg != nullptr || (filler.pinned_all() && filler.pinned_mapped());
-    // The next window is built (schedule step, fill tasks, SHA jobs, CRC items) on a helper
-    // thread while this one fills and enqueues the current one: with 14,336 live blobs the
-    // build is ~1.7 ms a window, 16 % of a page-cache files pass that was fill-bound.  Window
-    // wi always lands in staging slot wi % pl.n (Pipeline::next), so its addresses are known
-    // ahead.
-    struct Built {
-        std::vector<Filler::Task> tasks;
-        std::vector<ShaJob> jobs;
-        CrcBatch items;
-        size_t fill = 0;
-        double build_s = 0;
-    };
-    std::mutex bmu;
-    std::condition_variable bcv;
-    std::deque<Built> ready;
-    bool built_all = false, stop_build = false;
-    constexpr size_t kBuildAhead = 2;
-    std::thread builder([&] {
-        ItemBuilder B;
-        std::vector<WinChunk> win;
-        for (int bi = 0;; ++bi) {
-            {
-                std::unique_lock<std::mutex> lk(bmu);
-                bcv.wait(lk, [&] { return stop_build || ready.size() < kBuildAhead; });
-                if (stop_build) return;
-            }
-            const double tb = wall_s();
-            if (!sched.next(win)) break;
-            Window& w = pl.w[bi % pl.n];
-            Built bt;
-            bt.tasks.reserve(win.size());
-            bt.jobs.reserve(win.size());
-            for (const WinChunk& c : win) {
-                const uint64_t L = lens[c.blob];
-                const uint64_t dev = reinterpret_cast<uint64_t>(w.dev + bt.fill);
-                bt.tasks.push_back({c.blob, c.off, c.len, w.host + bt.fill});  // an empty blob too (its file is opened)
-                if (c.len && crc) B.add(bt.items, dev, c.off, c.off + c.len, L, (uint64_t)plens[c.blob], soff[c.blob]);
-                ShaJob j{};
-                j.ptr = dev;
-                j.len = c.len;
-                j.prefix = c.off;
-                j.out = c.blob;
-                j.flags = (c.off + c.len == L ? kShaFinal : 0) | (c.off ? kShaFromState : 0);
-                memcpy(j.h, kIV, sizeof kIV);
-                bt.jobs.push_back(j);
-                bt.fill += (c.len + place - 1) / place * place;
-            }
-            bt.build_s = wall_s() - tb;
-            std::lock_guard<std::mutex> g(bmu);
-            ready.push_back(std::move(bt));
-            bcv.notify_all();
-        }
-        std::lock_guard<std::mutex> g(bmu);
-        built_all = true;
-        bcv.notify_all();
-    });
-    struct BuilderJoin {
-        std::thread& t;
-        std::mutex& mu;
-        std::condition_variable& cv;
-        bool& stop;
-        ~BuilderJoin() {
-            {
-                std::lock_guard<std::mutex> g(mu);
-                stop = true;
-            }
-            cv.notify_all();
-            if (t.joinable()) t.join();
-        }
-    } builder_join{builder, bmu, bcv, stop_build};
-    int k = 0, wi = 0;
-    double t_acq = 0, t_build = 0, t_fill = 0, t_enq = 0, t_wait_build = 0;
-    const double t0 = wall_s();
-    while (!r) {
-        Built bt;
-        {
-            const double tw = wall_s();
-            std::unique_lock<std::mutex> lk(bmu);
-            bcv.wait(lk, [&] { return !ready.empty() || built_all; });
-            if (ready.empty()) break;  // every window built and run
-            bt = std::move(ready.front());
-            ready.pop_front();
-            bcv.notify_all();
-            t_wait_build += wall_s() - tw;
-        }
-        t_build += bt.build_s;
-        const double ta = wall_s();
-        r = pl.acquire(k);
-        if (r) break;
-        if (reg && wi >= pl.n) reg->copied(wi - pl.n);  // acquire waited for that window's copy
-        const double tb = wall_s();
-        t_acq += tb - ta;
-        Window& w = pl.w[k];
-        const std::vector<Filler::Task>& tasks = bt.tasks;
-        const size_t fill = bt.fill;
-        if (fill > w.cap) {  // the lease covers every window the schedule can build
-            set_error(KRK_EINVAL, "metainfo windows: window of %zu bytes exceeds the %zu-byte staging lease", fill,
-                      (size_t)w.cap);
-            r = KRK_EINVAL;
-            break;
-        }
-        const double tc = wall_s();
-        // page-locked sources go straight from the caller's memory into the device window: a
-        // DMA a chunk for a few wide chunks, else one gather launch (pinned blobs, or pageable
-        // ones once registered); the others through the pinned host window
-        const bool direct = !tasks.empty() && filler.pinned_all() && tasks.size() <= kDirectMaxCalls;
-        const bool gather = !direct && !tasks.empty() && gather_ok && (!reg || (gather_ok = reg->ready(wi)));
-        std::vector<CopyTask> dma;
-        std::vector<GatherSpan> spans;
-        if (direct) {
-            dma.reserve(tasks.size());
-            for (const Filler::Task& t : tasks)
-                if (t.len) dma.push_back({w.dev + (t.dst - w.host), filler.pinned_src(t.b, t.off), (size_t)t.len});
-        } else if (gather) {
-            spans.reserve(tasks.size());
-            for (const Filler::Task& t : tasks)
-                if (t.len) spans.push_back({w.dev + (t.dst - w.host), filler.src(t.b, t.off), t.len});
-        } else {
-            r = filler.fill(tasks);
-            if (r) break;
-        }
-        const double td = wall_s();
-        t_fill += td - tc;
-        ++st->windows;
-        st->direct_windows += direct;
-        st->gather_windows += gather;
-        hipError_t up = hipSuccess;
-        if (gather) {
-            r = pl.h2d_gather(D, k, spans, cp);
-            if (r) break;
-        } else {
-            up = direct ? pl.h2d_direct(k, dma, cp) : pl.h2d(k, fill, cp);
-        }
-        if (up != hipSuccess || hipStreamWaitEvent(ks, w.copied, 0) != hipSuccess ||
-            (crc && hipStreamWaitEvent(kc, w.copied, 0) != hipSuccess)) {
-            set_error(KRK_EHIP, "metainfo windows: staging copy failed");
-            r = KRK_EHIP;
-            break;
-        }
-        r = run_jobs(D, bt.jobs, d_dig, d_state, ks);
-        if (!r && crc) r = run_items(D, bt.items, d_sums, kc);
-        if (r) break;
-        // the device window is free again once both kernels have read it
-        pl.release(k, 0, ks);
-        if (crc) pl.release(k, 1, kc);
-        t_enq += wall_s() - td;
-        k = pl.next(k);
-        ++wi;
-    }
-    {
-        std::lock_guard<std::mutex> g(bmu);
-        stop_build = true;
-    }
-    bcv.notify_all();
-    builder.join();
-    st->max_live = sched.max_live();
-    st->loop_s = wall_s() - t0;
-    st->acquire_s = t_acq;
-    st->fill_s = t_fill;
-    st->enqueue_s = t_enq;
-    if (reg) {
-        st->registered_bytes = reg->registered_bytes();
-        st->register_s = reg->register_seconds();
-    }
-    if (trace_on())
-        fprintf(stderr,
-                "krk_trace windows: windows=%d W=%zu max_live=%llu loop=%.3fs acquire=%.3fs build=%.3fs (ahead; "
-                "waited %.3fs) fill=%.3fs enqueue=%.3fs\n",
-                st->windows, W, (unsigned long long)st->max_live, wall_s() - t0, t_acq, t_build, t_wait_build, t_fill,
-                t_enq);
-    return r;
-}
+thread_local PassStats t_last_call;
 
 // KRK_HOST_GATHER: 0 = host-buffer calls always stage; 1 = gather pageable blobs too
 // (registered for the call: host_register.hpp); unset (AUTO) = gather page-locked blobs'
@@ -464,36 +57,6 @@ int host_gather_mode() {
     return g_host_gather.load();
 }
 
-// The MemFiller of a host-buffer call: page-locked blobs DMA'd or gathered as they are,
-// pageable ones registered for the gather (KRK_HOST_GATHER) or staged.
-void setup_mem_filler(MemFiller& f, const krk_blob* blobs, uint64_t n, const std::vector<char>& on_host, Device* D) {
-    // KRK_PINNED_DIRECT=0 stages pinned sources too (A/B)
-    static const bool allow_direct = !KRK_AB_ENV("KRK_PINNED_DIRECT") || atoi(KRK_AB_ENV("KRK_PINNED_DIRECT")) != 0;
-    const int gm = host_gather_mode();
-    f.pinned = allow_direct;
-    uint64_t first = n;
-    for (uint64_t i = 0; i < n; ++i) {
-        if (on_host[i] || !blobs[i].length) continue;
-        if (first == n) first = i;
-        if (f.pinned && !host_pinned(blobs[i].data, blobs[i].length)) f.pinned = false;
-    }
-    if (first == n) return;
-    f.mapped = f.pinned && gm != 0;  // every windowed blob at its host address
-    MappedAtHost at_host;
-    for (uint64_t i = first; f.mapped && i < n; ++i)
-        if (!on_host[i]) f.mapped = at_host(blobs[i].data, blobs[i].length);
-    if (!f.pinned && gm == 1) {
-        std::vector<std::pair<uintptr_t, uintptr_t>> ranges;
-        for (uint64_t i = 0; i < n; ++i)
-            if (!on_host[i] && blobs[i].length) {
-                const uintptr_t a = reinterpret_cast<uintptr_t>(blobs[i].data);
-                ranges.push_back({a, a + blobs[i].length});
-            }
-        f.reg = std::make_unique<HostRegistry>(std::move(ranges));
-        f.gather_stream = D->s_main;  // windows_pass's copy stream
-    }
-}
-
 // Every host-buffer entry point, once its streams have drained and before any copy-out: the
 // registry's helpers stopped and every caller range it registered released.  A HIP copy whose
 // destination starts in a registered page and runs past it is refused ("copy-out failed:
@@ -501,7 +64,7 @@ void setup_mem_filler(MemFiller& f, const krk_blob* blobs, uint64_t n, const std
 // so with the last windows' segments still registered an output array -- or any heap buffer
 // -- sharing a page with a small blob was such a destination.  The count left registered is
 // kept for krk_windows_last_copyout (0 by construction).
-void release_caller_pages(MemFiller& f, CallStats* st) {
+void release_caller_pages(MemSource& f, PassStats* st) {
     if (!f.reg) return;
     f.reg->finish(f.gather_stream);
     st->live_at_copyout = f.reg->live_segments();
@@ -540,7 +103,6 @@ uint64_t direct_live_cap(Device* D) {
     return std::min(live_cap_for(D), std::max<uint64_t>(256, (need + 63) / 64 * 64));
 }
 
-
 }  // namespace
 
 }  // namespace krk
@@ -549,7 +111,7 @@ using namespace krk;
 
 // What krk_metainfo_digest_host, krk_sha256_host and krk_metainfo_digest_files share: the
 // device results, the host offload's share with its thread and results, the caller's arrays.
-// An entry point checks its arguments, then plan(), start(), its filler, run().
+// An entry point checks its arguments, then plan(), start(), its source, run().
 namespace {
 struct WindowCall {
     const char* name;  // the entry point, in its error texts
@@ -560,7 +122,7 @@ struct WindowCall {
     std::vector<uint64_t> lens, soff;
     std::vector<int64_t> plens;
     uint64_t lo = 0, hi = 0;  // the sums span
-    double resident = -1;       // file batches: CallStats' resident and direct_reads
+    double resident = -1;       // file batches: PassStats' resident and direct_reads
     bool direct_reads = false;
     uint8_t* d_dig = nullptr;  // the device's results
     uint32_t *d_state = nullptr, *d_sums = nullptr;
@@ -631,14 +193,36 @@ struct WindowCall {
         // a CPU quota throttles the whole process.
         t_host_share = std::max(4, host_threads_for_call() - off_t);
     }
-    // The windows, then both sides' results into the caller's arrays.  mem_filler: the filler
-    // when it reads caller memory (its registrations are released before any copy-out).
-    int run(Device* D, Filler& filler, MemFiller* mem_filler, uint64_t align, uint64_t cap) {
-        CallStats st;
-        int r = windows_pass(D, n, lens.data(), plens.data(), soff.data(), on_host, filler, align, cap, d_sums, d_dig,
-                             d_state, &st, crc);
+    // The windows of the blobs the host did not take (WindowSched: `cap` live, chunks a multiple
+    // of `align`), copied on s_main with SHA-256 on s_a and CRC on s_b, then both sides' results
+    // into the caller's arrays.
+    template <class Source>
+    int run(Device* D, Source& src, uint64_t align, uint64_t cap) {
+        PassStats st;
         st.resident = resident;
         st.direct_reads = direct_reads;
+        std::vector<uint32_t> blobs;
+        for (uint64_t i = 0; i < n; ++i)
+            if (!on_host[i]) blobs.push_back((uint32_t)i);
+        int r = KRK_OK;
+        HostRegistry* reg = nullptr;
+        if (!blobs.empty()) {
+            const size_t W = window_bytes();
+            const uint64_t live_cap = std::min<uint64_t>(cap, blobs.size());
+            WindowSched sched(lens.data(), blobs, W, live_cap, align);
+            const size_t place = std::max<uint64_t>(align == 64 ? 16 : align, 16);  // chunk start alignment in the window
+            // a window holds about W bytes, but never less than one minimum chunk (the schedule's
+            // alignment) a live blob, each rounded up to `place` (a small KRK_WINDOW_MB
+            // or a large KRK_LIVE_CAP made live x 64 > W + 16 x live)
+            const uint64_t span = std::max<uint64_t>(W, live_cap * std::max<uint64_t>(align, 64)) + place * live_cap;
+            if constexpr (Source::kMemory)
+                if ((reg = src.reg.get())) src.announce(WindowSched(lens.data(), blobs, W, live_cap, align));
+            const WindowPass pass{"metainfo windows", D, [&](std::vector<WinChunk>& w) { return sched.next(w); }, place,
+                                  span, D->s_main, D->s_a, crc ? D->s_b : nullptr, lens.data(), plens.data(), soff.data(),
+                                  d_dig, d_state, d_sums, /*build_ahead=*/2, &st};
+            r = run_windows(pass, src);
+            st.max_live = sched.max_live();
+        }
         // drain what was queued even after a read error (the windows' kernels read the buffers)
         const bool synced = hipStreamSynchronize(D->s_a) == hipSuccess &&
                             (!crc || hipStreamSynchronize(D->s_b) == hipSuccess) &&
@@ -647,9 +231,9 @@ struct WindowCall {
             set_error(KRK_EHIP, "%s: sync failed", name);
             r = KRK_EHIP;
         }
-        if (mem_filler) release_caller_pages(*mem_filler, &st);
-        if (!r) r = copy_out(digests_host, d_dig, n * 32, filler.registry(), "digest");
-        if (!r && hi > lo) r = copy_out(sums_host + lo, d_sums + lo, (hi - lo) * 4, filler.registry(), "sums");
+        if constexpr (Source::kMemory) release_caller_pages(src, &st);
+        if (!r) r = copy_out(digests_host, d_dig, n * 32, reg, "digest");
+        if (!r && hi > lo) r = copy_out(sums_host + lo, d_sums + lo, (hi - lo) * 4, reg, "sums");
         if (host_th.joinable()) host_th.join();
         if (!r && host_rc) {
             t_err = host_err;
@@ -663,6 +247,15 @@ struct WindowCall {
         st.host_blobs = host.size();
         t_last_call = st;
         return r;
+    }
+    // run() from the caller's buffers: page-locked blobs DMA'd or gathered as they are, pageable
+    // ones registered for the gather (KRK_HOST_GATHER) or staged.
+    int run_memory(Device* D, const krk_blob* blobs) {
+        // KRK_PINNED_DIRECT=0 stages pinned sources too (A/B)
+        static const bool allow_direct = !KRK_AB_ENV("KRK_PINNED_DIRECT") || atoi(KRK_AB_ENV("KRK_PINNED_DIRECT")) != 0;
+        MemSource src(blobs, n);
+        src.setup(on_host, allow_direct && src.all_pinned(on_host), host_gather_mode(), D->s_main);
+        return run(D, src, 64, live_cap_for(D));
     }
 };
 }  // namespace
@@ -745,9 +338,7 @@ int krk_metainfo_digest_host(const krk_blob* blobs, uint64_t n, uint32_t* sums_h
         offload_whole_host(p, l, pl, so, c.off_t, c.host_dig.data());
         return KRK_OK;
     });
-    MemFiller filler(blobs);
-    setup_mem_filler(filler, blobs, n, c.on_host, D);
-    return c.run(D, filler, &filler, 64, live_cap_for(D));
+    return c.run_memory(D, blobs);
 }
 
 // Whole-blob SHA-256 of host buffers (the Digester over many uploads at once): the same
@@ -770,9 +361,7 @@ int krk_sha256_host(const uint8_t* const* data_host, const uint64_t* lengths, ui
         offload_hash_host(p, l, c.off_t, c.host_dig.data());
         return KRK_OK;
     });
-    MemFiller filler(blobs.data());
-    setup_mem_filler(filler, blobs.data(), n, c.on_host, D);
-    return c.run(D, filler, &filler, 64, live_cap_for(D));
+    return c.run_memory(D, blobs.data());
 }
 
 // The page-cache resident share of a file batch, from up to 64 evenly spaced files' first
@@ -836,11 +425,11 @@ int krk_metainfo_digest_files(const krk_file_blob* files, uint64_t n, uint32_t* 
     // the page cache.
     const char* fd_env = KRK_OP_ENV("KRK_FILE_DIRECT");
     const bool direct = c.direct_reads = fd_env ? atoi(fd_env) > 0 : cold;
-    FileFiller filler(files, n, direct);
+    FileSource src(files, n, direct, /*async=*/true);
     // at most as many live blobs as this call holds file descriptors (a lease of the
     // process's budget, shared with every other file batch running now)
     FdLease fds(std::min<uint64_t>(direct ? direct_live_cap(D) : live_cap_for(D), n));
-    return c.run(D, filler, nullptr, direct ? 4096 : 64, fds.n);
+    return c.run(D, src, direct ? 4096 : 64, fds.n);
 }
 
 int krk_windows_last_call(uint64_t* max_live, int* windows, uint64_t* host_blobs) {

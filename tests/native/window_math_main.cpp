@@ -12,6 +12,13 @@
 //  2. cut_span with copy_span_bytes / read_span_bytes (what par_copy and par_read run) over T = 1 ... 17: the
 //     pieces cover each task's bytes exactly once and in order; padded, every piece starts on a 4 KiB multiple of
 //     its task and ends on one or at the task's end.
+//  3. PackSched against a byte walk.  Lists of n <= 4 blobs; place 16 and 4096; W in {place, 3 place, 8 place};
+//     lengths from the nine values at which the packing can change course {0, 1, place - 1, place, place + 1,
+//     W - 1, W, W + 1, 2 W + 1} (2 x 3 x (1 + 9 + 81 + 729 + 6,561) = 44,286 lists).  Required of every schedule:
+//     each blob's bytes are covered exactly once and in order with blobs in index order, no chunk is empty, every
+//     chunk starts on a multiple of place in its window (placed as the pass places them: chunk k + 1 at
+//     pos_k + round_up(len_k, place)) and ends at or before W, every window but the last is full (its rounded
+//     fill equals W), and the schedule ends.
 #include <stdio.h>
 
 #include "../../kraken_amd/csrc/window_math.hpp"
@@ -202,11 +209,69 @@ static void cuts() {
     }
 }
 
+// ---------------------------------------------------------------- the packing schedule
+static long g_pack_windows = 0;
+static void pack(const std::vector<uint64_t>& L, uint64_t W, uint64_t place) {
+    ++g_cases;
+    uint64_t total = 0;
+    for (uint64_t l : L) total += l;
+    PackSched s(L.data(), L.size(), W, place);
+    std::vector<WinChunk> win;
+    size_t b = 0;       // the blob the walk stands in
+    uint64_t off = 0;   // ... and the bytes of it covered
+    bool short_window = false;
+    for (uint64_t wi = 0; s.next(win); ++wi) {
+        ++g_pack_windows;
+        CHECK(wi <= total, "schedule does not end");  // every window carries a byte
+        if (wi > total) return;
+        CHECK(!short_window, "window %llu follows one that was not full", (unsigned long long)wi);
+        CHECK(!win.empty(), "window %llu is empty", (unsigned long long)wi);
+        uint64_t fill = 0;
+        for (const WinChunk& c : win) {
+            while (b < L.size() && off == L[b]) ++b, off = 0;  // blobs in index order, empty ones passed over
+            CHECK(c.len > 0, "empty chunk of blob %u", c.blob);
+            CHECK(b < L.size() && c.blob == b && c.off == off, "chunk of blob %u at %llu, the walk stands in blob %zu at %llu",
+                  c.blob, (unsigned long long)c.off, b, (unsigned long long)off);
+            if (b >= L.size() || c.blob != b) return;
+            CHECK(c.off + c.len <= L[b], "blob %u: chunk ends at %llu of %llu", c.blob, (unsigned long long)(c.off + c.len),
+                  (unsigned long long)L[b]);
+            CHECK(fill % place == 0 && fill + c.len <= W, "chunk of %llu bytes at +%llu of a window of %llu",
+                  (unsigned long long)c.len, (unsigned long long)fill, (unsigned long long)W);
+            off = c.off + c.len;
+            fill += (c.len + place - 1) / place * place;
+        }
+        short_window = fill != W;
+    }
+    while (b < L.size() && off == L[b]) ++b, off = 0;
+    CHECK(b == L.size(), "the schedule ended in blob %zu at %llu", b, (unsigned long long)off);
+}
+
+static void packs() {
+    for (uint64_t place : {uint64_t(16), uint64_t(4096)})
+        for (uint64_t W : {place, 3 * place, 8 * place}) {
+            const uint64_t edge[9] = {0, 1, place - 1, place, place + 1, W - 1, W, W + 1, 2 * W + 1};
+            pack({}, W, place);
+            for (uint64_t a : edge) {
+                pack({a}, W, place);
+                for (uint64_t b : edge) {
+                    pack({a, b}, W, place);
+                    for (uint64_t c : edge) {
+                        pack({a, b, c}, W, place);
+                        for (uint64_t d : edge) pack({a, b, c, d}, W, place);
+                    }
+                }
+            }
+        }
+}
+
 int main() {
     schedules();
     const long sched_cases = g_cases;
     cuts();
-    printf("window_math: %ld schedules (%ld windows, %ld drops), %ld cuts (%ld pieces), %ld mismatches\n", sched_cases,
-           g_windows, g_drops, g_cases - sched_cases, g_pieces, g_bad);
+    const long cut_cases = g_cases - sched_cases;
+    packs();
+    printf("window_math: %ld schedules (%ld windows, %ld drops), %ld cuts (%ld pieces), %ld packings (%ld windows), "
+           "%ld mismatches\n",
+           sched_cases, g_windows, g_drops, cut_cases, g_pieces, g_cases - sched_cases - cut_cases, g_pack_windows, g_bad);
     return g_bad ? 1 : 0;
 }

@@ -1,6 +1,6 @@
-"""The window matrix (tests/window_matrix.py) on the device: the host-resident window passes -- windows_pass of
-windows.cpp, the two packers of crc_host.cpp, the slot ring, par_copy and par_read of staging.hpp -- at their chunk,
-slot and transport edges.  Every output array is compared whole (canaries on both sides, prefilled with 0xFF) against
+"""The window matrix (tests/window_matrix.py) on the device: the host-resident window passes -- run_windows of
+window_pass.cpp under WindowSched (the digest calls of windows.cpp) and PackSched (the CRC-only calls of
+crc_host.cpp), the slot ring, par_copy and par_read of staging.hpp -- at their chunk, slot and transport edges.  Every output array is compared whole (canaries on both sides, prefilled with 0xFF) against
 hashlib.sha256 / zlib.crc32 images, a mismatch names the blob, the piece and the windows, slots and chunks its bytes
 went through, and krk_windows_last_* must equal the Python replay of the schedule after every call.
 

@@ -1,6 +1,6 @@
-"""tests/native/window_math_main.cpp: the window schedule and the per-thread span cutting of the host-resident window
-passes (kraken_amd/csrc/window_math.hpp: WindowSched, what windows.cpp runs every window by, and cut_span, what
-par_copy and par_read of staging.hpp split a window's fill with) as a stand-alone CPU program (its own main, nothing
+"""tests/native/window_math_main.cpp: the two schedules and the per-thread span cutting of the host-resident window
+passes (kraken_amd/csrc/window_math.hpp: WindowSched and PackSched, what window_pass.cpp runs every window by, and
+cut_span, what par_copy and par_read of staging.hpp split a window's fill with) as a stand-alone CPU program (its own main, nothing
 of the library linked) built with AddressSanitizer and UndefinedBehaviorSanitizer and run directly."""
 import os
 import subprocess

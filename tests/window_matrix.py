@@ -1,8 +1,9 @@
 """The window matrix: the host-resident window passes pinned at their chunk, slot and transport edges.
 
-What is pinned: `windows_pass` (kraken_amd/csrc/windows.cpp: krk_metainfo_digest_host, krk_sha256_host,
-krk_metainfo_digest_files), the two sequential packers of kraken_amd/csrc/crc_host.cpp (krk_piece_sums_host,
-krk_piece_sums_files) and the slot ring, par_copy and par_read of kraken_amd/csrc/staging.hpp.  That code decides what
+What is pinned: `run_windows` (kraken_amd/csrc/window_pass.cpp) under both of its schedules -- WindowSched for the
+digest calls of windows.cpp (krk_metainfo_digest_host, krk_sha256_host, krk_metainfo_digest_files), PackSched for the
+CRC-only calls of crc_host.cpp (krk_piece_sums_host, krk_piece_sums_files) -- with its memory and file sources, and
+the slot ring, par_copy and par_read of kraken_amd/csrc/staging.hpp.  That code decides what
 the SHA-256 and CRC kernels are asked to do window by window: SHA jobs chained from midstates, CRC items for byte
 ranges that start and end inside pieces, chunks placed 16 B or 4 KiB apart in a slot reused every third window, one of
 four ways up (staged, a DMA a chunk, the gather over page-locked or over registered pageable memory) and three ways
@@ -80,8 +81,8 @@ def replay(lens, W, cap, align=64, max_chunk=None, blobs=None):
 
 
 def pack_replay(lens, W, place):
-    """The sequential packers of crc_host.cpp restated: windows of (blob, boff, take, fill), fill rounded up to
-    `place` (16: memory, 4096: files) after every portion; a zero-length blob takes nothing."""
+    """PackSched (window_math.hpp, the CRC-only calls of crc_host.cpp) restated: windows of (blob, boff, take, fill),
+    fill rounded up to `place` (16: memory, 4096: files) after every portion; a zero-length blob takes nothing."""
     windows, bi, boff, n = [], 0, 0, len(lens)
     while bi < n:
         fill, win = 0, []
@@ -173,11 +174,13 @@ ALL_TAGS = frozenset(
      "3 x ring + 1 windows"] + ["final from state, len%%64=%d" % r for r in SHA_TAILS])
 
 
-def pack_tags(windows, lens, plens, place, W=W1):
+def pack_tags(windows, lens, plens, place, W=W1, ring=RING):
     """The edges of a packed schedule (group F)."""
     out = set()
     if len(windows) >= 10:
         out.add("ten windows")
+    if len(windows) >= 3 * ring + 1:  # every slot of the ring refilled three times over
+        out.add("3 x ring + 1 windows")
     prev_zero = False
     for L in lens:
         if L and prev_zero:
@@ -197,7 +200,7 @@ def pack_tags(windows, lens, plens, place, W=W1):
     return out
 
 
-F_TAGS = frozenset(["ten windows", "empty blob between", "boundary at a piece edge",
+F_TAGS = frozenset(["ten windows", "3 x ring + 1 windows", "empty blob between", "boundary at a piece edge",
                     "boundary one place before a piece edge", "boundary one place after a piece edge",
                     "blob ends at the window's end", "portion shorter than place"])
 
