@@ -661,6 +661,68 @@ int krk_ring_select_dev(const uint8_t* digests32_dev, uint64_t n, const uint64_t
                         const uint64_t* or_bits_dev, uint64_t* bits_out, uint64_t* idx_out,
                         uint64_t idx_cap, uint64_t* count_out, void* stream);
 
+/* ------------------------------------- cleanup plans from a raw cache listing
+ * A cache listing is hex names and mtimes, not raw digests and a ready `expired` bitset: the
+ * SHA-256 hex codec (core.NewSHA256DigestFromHex / ValidateSHA256 / Digest.Hex(),
+ * core/digest.go:57-68,143-161), the expiry comparison of maybeDelete
+ * (origin/blobserver/server.go:686-759) and of the store's TTL/TTI rule readyForDeletion
+ * (lib/store/cleanup.go:112-155, with its _last_access_time sidecar,
+ * lib/store/metadata/last_access_time.go:55-70), and the two fused with the ring selection.
+ *
+ * Listing layout (the names / name_off convention of krk_metainfo_batch_dev): `names` is bytes
+ * back to back, `off` is n + 1 uint64 values, name i is names[off[i], off[i+1]); off[0] need not
+ * be 0.  A name's length is the unsigned 64-bit difference off[i+1] - off[i]; any value but 64
+ * is a length error and no byte of that name is read.  Then the 32 pairs are decoded in index
+ * order, either case accepted; the first byte, in index order, that is not [0-9a-fA-F] is the
+ * error (encoding/hex's InvalidByteError).  One status word a name:
+ *   0                                        valid
+ *   KRK_DHEX_LEN | min(len, 0x3FFFFFFF)      len != 64
+ *   KRK_DHEX_BYTE | p << 8 | byte            bad byte at position p (0..63)
+ * An invalid name's digest is 32 zero bytes (every output byte is stored) and its bit in the
+ * `valid` bitset is 0; the bitset has krk_bitfield_words(n) words in the layout above, tail bits
+ * 0, every word stored.  Times are int64 nanoseconds; expired(now, t, d) = sat_sub(now, t) > d,
+ * the subtraction saturating at the int64 limits as time.Time.Sub does, the comparison strict. */
+#define KRK_DHEX_LEN 0x40000000u
+#define KRK_DHEX_BYTE 0x80000000u
+#define KRK_NO_TIME INT64_MIN   /* a missing _last_access_time */
+/* Host forms; no device.  status_out and valid_out may be NULL. */
+int krk_digest_parse_hex(const uint8_t* names, const uint64_t* off, uint64_t n, uint8_t* digests32_out,
+                         uint32_t* status_out, uint64_t* valid_out);
+/* Digest.Hex(): 64 lowercase characters a digest at stride 64, no terminator. */
+int krk_digest_format_hex(const uint8_t* digests32, uint64_t n, uint8_t* hex_out);
+/* bit i = (mtime_ns && expired(now, mtime_ns[i], ttl)) ||
+ *         (atime_ns && atime_ns[i] != KRK_NO_TIME && expired(now, atime_ns[i], tti));
+ * either column may be NULL.  maybeDelete passes mtime only; cleanup.go's scan passes mtime only
+ * when ttl > 0, together with the access-time column.  krk_bitfield_words(n) words, tail bits 0. */
+int krk_expiry_bits(const int64_t* mtime_ns, const int64_t* atime_ns, uint64_t n, int64_t now_ns,
+                    int64_t ttl_ns, int64_t tti_ns, uint64_t* bits_out);
+/* maybeDelete over ListCacheFiles() from the listing itself:
+ *   sel(i) = valid(i) & ((mask[ShardID(d_i)] ^ (invert != 0)) | expired(now, mtime_ns[i], ttl)).
+ * mtime_ns may be NULL: no expiry term (a krk_ring_mask_moved mask then answers "which names of
+ * this listing change hands").  An invalid name is never selected.  bits_out, idx_out, idx_cap
+ * and count_out as krk_ring_select: ascending listing positions (positions in the listing
+ * itself: no compaction, no mapping back), truncation reported by count > idx_cap, the count
+ * always stored.  valid_out may be NULL.  A NULL argument that is not nullable, or idx_out NULL
+ * with idx_cap != 0, is KRK_EINVAL before any output is touched. */
+int krk_cleanup_plan(const uint8_t* names, const uint64_t* off, uint64_t n, const int64_t* mtime_ns,
+                     int64_t now_ns, int64_t ttl_ns, const uint64_t* mask, int invert, uint64_t* bits_out,
+                     uint64_t* valid_out, uint64_t* idx_out, uint64_t idx_cap, uint64_t* count_out);
+/* The same on the device (digest_hex.hip), byte for byte and bit for bit; asynchronous on
+ * `stream`.  Every device-side pointer is device memory or page-locked host memory
+ * (krk_host_alloc); off, mtime, valid, bits, idx and count 8-byte aligned, status 4-byte aligned;
+ * anything else is KRK_EINVAL before anything is launched.  Names start at any byte alignment and
+ * no byte outside names[off[0], off[n]) is read; digests32_dev and hex_dev may have any
+ * alignment; all offsets are 64-bit.  status_dev, valid_dev, mtime_ns_dev and valid_out may be
+ * NULL.  mask_host is copied into the library's staging before the call returns.  KRK_ENODEV
+ * without a gfx950 device: there is no fall-back to the host forms. */
+int krk_digest_parse_hex_dev(const uint8_t* names_dev, const uint64_t* off_dev, uint64_t n,
+                             uint8_t* digests32_dev, uint32_t* status_dev, uint64_t* valid_dev, void* stream);
+int krk_digest_format_hex_dev(const uint8_t* digests32_dev, uint64_t n, uint8_t* hex_dev, void* stream);
+int krk_cleanup_plan_dev(const uint8_t* names_dev, const uint64_t* off_dev, uint64_t n,
+                         const int64_t* mtime_ns_dev, int64_t now_ns, int64_t ttl_ns, const uint64_t* mask_host,
+                         int invert, uint64_t* bits_out, uint64_t* valid_out, uint64_t* idx_out,
+                         uint64_t idx_cap, uint64_t* count_out, void* stream);
+
 /* ------------------------------------------------ device memory helpers
  * For callers (benchmarks, cgo) that do not own a device allocator. */
 int krk_dev_alloc(uint64_t bytes, void** out);

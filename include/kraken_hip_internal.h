@@ -242,6 +242,11 @@ int krk_metainfo_json_geometry(uint64_t* serialize_unit_sums, uint64_t* parse_un
  * 64-bit carry runs between passes), and the workgroups a launch has at the most (with more units,
  * or more blobs for the parse status, the waves stride).  No device. */
 int krk_metainfo_json_scan_geometry(uint64_t* counts_per_pass, uint64_t* max_workgroups);
+/* The shape of digest_hex.hip as built (kernel names "digest_parse_hex", "digest_format_hex";
+ * "cleanup_plan" has krk_ring_select_geometry's): the names one workgroup of
+ * krk_digest_parse_hex_dev / krk_digest_format_hex_dev takes, for the tests that pin their edges.
+ * No device. */
+int krk_digest_hex_geometry(uint64_t* names_per_workgroup);
 
 /* ------------------------------------------------------- SHA-256 plans
  * Lanes per stream (1, 2 or 8) the library uses for a batch of n_streams streams on

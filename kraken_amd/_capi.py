@@ -196,6 +196,16 @@ def _load() -> C.CDLL:
         "krk_ring_select": (i, [u8p, C.c_uint64, u64p, i, u64p, u64p, u64p, C.c_uint64, u64p]),
         "krk_ring_select_dev": (i, [vp, C.c_uint64, u64p, i, vp, vp, vp, C.c_uint64, vp, vp]),
         "krk_ring_select_geometry": (i, [u64p, u64p]),
+        "krk_digest_parse_hex": (i, [vp, u64p, C.c_uint64, vp, u32p, u64p]),
+        "krk_digest_format_hex": (i, [vp, C.c_uint64, vp]),
+        "krk_expiry_bits": (i, [i64p, i64p, C.c_uint64, C.c_int64, C.c_int64, C.c_int64, u64p]),
+        "krk_cleanup_plan": (i, [vp, u64p, C.c_uint64, i64p, C.c_int64, C.c_int64, u64p, i, u64p, u64p, u64p,
+                                 C.c_uint64, u64p]),
+        "krk_digest_parse_hex_dev": (i, [vp, vp, C.c_uint64, vp, vp, vp, vp]),
+        "krk_digest_format_hex_dev": (i, [vp, C.c_uint64, vp, vp]),
+        "krk_cleanup_plan_dev": (i, [vp, vp, C.c_uint64, vp, C.c_int64, C.c_int64, u64p, i, vp, vp, vp, C.c_uint64,
+                                     vp, vp]),
+        "krk_digest_hex_geometry": (i, [u64p]),
         "krk_synth_fill_dev": (i, [vp, C.c_uint64, C.c_uint64, C.c_uint64, i, vp]),
         "krk_synth_fill_chunks_dev": (i, [C.POINTER(krk_chunk), C.c_uint64, i, vp]),
         "krk_dev_alloc": (i, [C.c_uint64, C.POINTER(vp)]),

@@ -320,6 +320,40 @@ inline uint64_t ring_select_scratch_bytes(uint64_t n) {
 hipError_t launch_ring_select(const uint8_t* digests32, uint64_t n, const uint32_t* mask, int invert,
                               const uint64_t* or_bits, uint64_t* bits, uint64_t* idx, uint64_t idx_cap,
                               uint64_t* count_out, void* scratch, hipStream_t s);
+// The scratch of a selection over n digests: [tile_base u64 x tiles][workgroup counts, then
+// offsets, u32 x workgroups][tile_sum u32 x tiles].
+struct SelectScratch {
+    uint64_t* tile_base;
+    uint32_t* wg_count;
+    uint32_t* tile_sum;
+};
+inline SelectScratch select_scratch(void* scratch, uint64_t n) {
+    uint64_t* tile_base = static_cast<uint64_t*>(scratch);
+    uint32_t* wg_count = reinterpret_cast<uint32_t*>(tile_base + ring_select_tiles(n));
+    return {tile_base, wg_count, wg_count + ring_select_workgroups(n)};
+}
+// Phases 2 and 3 of a selection whose phase 1 has stored the bitset's words and the workgroup
+// counts (wg_count[b] = the set bits of words [kSelectW / 64 b, + kSelectW / 64)): the scan,
+// *count_out, and the index list.  launch_ring_select's own tail, and launch_cleanup_plan's.
+hipError_t launch_select_scan_scatter(uint64_t n, const uint64_t* bits, uint64_t* idx, uint64_t idx_cap,
+                                      uint64_t* count_out, void* scratch, hipStream_t s);
+
+// ---------------------------------------------------------------- digest hex, cleanup plan
+// A cache listing's text (digest_hex.hip, digest_hex_math.hpp): name i is names[off[i], off[i + 1]),
+// 64 hex digits when valid.  parse: digests32[32 i, + 32) (zero for an invalid name; any
+// alignment), status[i] (nullable) and valid (nullable, the bitset of "status 0", tail bits 0),
+// every documented byte stored.  format: hex[64 i, + 64) lowercase, any alignment both sides.
+// A workgroup takes kDhexW names.
+constexpr uint32_t kDhexW = 1024;
+hipError_t launch_digest_parse_hex(const uint8_t* names, const uint64_t* off, uint64_t n, uint8_t* digests32,
+                                   uint32_t* status, uint64_t* valid, hipStream_t s);
+hipError_t launch_digest_format_hex(const uint8_t* digests32, uint64_t n, uint8_t* hex, hipStream_t s);
+// sel(i) = valid(i) & ((mask[ShardID(d_i)] ^ invert) | expired(now, mtime[i], ttl)) (mtime
+// nullable: no expiry term) over the listing's text: bits, idx, idx_cap, count_out, mask and
+// scratch as launch_ring_select, valid (nullable) as launch_digest_parse_hex.
+hipError_t launch_cleanup_plan(const uint8_t* names, const uint64_t* off, uint64_t n, const int64_t* mtime, int64_t now,
+                               int64_t ttl, const uint32_t* mask, int invert, uint64_t* bits, uint64_t* valid,
+                               uint64_t* idx, uint64_t idx_cap, uint64_t* count_out, void* scratch, hipStream_t s);
 
 // ---------------------------------------------------------------- synthetic data
 // One synthetic chunk: bytes [offset, offset + n) of the blob whose stream seed is `seed`.

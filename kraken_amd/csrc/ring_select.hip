@@ -159,36 +159,41 @@ ring_select_scatter_kernel(const uint64_t* __restrict__ bits, uint64_t n_words, 
 
 }  // namespace
 
+hipError_t launch_select_scan_scatter(uint64_t n, const uint64_t* bits, uint64_t* idx, uint64_t idx_cap,
+                                      uint64_t* count_out, void* scratch, hipStream_t s) {
+    const uint64_t n_wg = ring_select_workgroups(n), n_tiles = ring_select_tiles(n);
+    const SelectScratch sc = select_scratch(scratch, n);
+    if (n_wg) {
+        hipLaunchKernelGGL(ring_select_scan_tiles_kernel, dim3((uint32_t)n_tiles), dim3(kBlock), 0, s, sc.wg_count, n_wg,
+                           sc.tile_sum);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(ring_select_scan_sums_kernel, dim3(1), dim3(kBlock), 0, s, sc.tile_sum, n_tiles, sc.tile_base,
+                       count_out);  // n == 0: stores the 0
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess || !n_wg || !idx_cap) return e;
+    hipLaunchKernelGGL(ring_select_scatter_kernel, dim3((uint32_t)n_wg), dim3(kBlock), 0, s, bits, (n + 63) / 64,
+                       sc.wg_count, sc.tile_base, idx, idx_cap);
+    return hipGetLastError();
+}
+
 hipError_t launch_ring_select(const uint8_t* digests32, uint64_t n, const uint32_t* mask, int invert,
                               const uint64_t* or_bits, uint64_t* bits, uint64_t* idx, uint64_t idx_cap,
                               uint64_t* count_out, void* scratch, hipStream_t s) {
-    const uint64_t n_wg = ring_select_workgroups(n), n_tiles = ring_select_tiles(n);
+    const uint64_t n_wg = ring_select_workgroups(n);
     if (n_wg > 0x7FFFFFFFull) return hipErrorInvalidValue;
     const hipError_t pre = launch_precheck();
     if (pre != hipSuccess) return pre;
     t_launch_plan = 0;
     t_launch_units = n;
-    // scratch: [tile_base u64 x n_tiles][wg counts -> offsets u32 x n_wg][tile_sum u32 x n_tiles]
-    uint64_t* tile_base = static_cast<uint64_t*>(scratch);
-    uint32_t* wg_count = reinterpret_cast<uint32_t*>(tile_base + n_tiles);
-    uint32_t* tile_sum = wg_count + n_wg;
     if (n_wg) {
         hipLaunchKernelGGL(ring_select_bits_kernel, dim3((uint32_t)n_wg), dim3(kBlock), 0, s, digests32, n, mask,
-                           invert ? 1u : 0u, or_bits, bits, wg_count);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(ring_select_scan_tiles_kernel, dim3((uint32_t)n_tiles), dim3(kBlock), 0, s, wg_count, n_wg,
-                           tile_sum);
-        e = hipGetLastError();
+                           invert ? 1u : 0u, or_bits, bits, select_scratch(scratch, n).wg_count);
+        const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(ring_select_scan_sums_kernel, dim3(1), dim3(kBlock), 0, s, tile_sum, n_tiles, tile_base,
-                       count_out);  // n == 0: stores the 0
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess || !n_wg || !idx_cap) return e;
-    hipLaunchKernelGGL(ring_select_scatter_kernel, dim3((uint32_t)n_wg), dim3(kBlock), 0, s, bits, (n + 63) / 64,
-                       wg_count, tile_base, idx, idx_cap);
-    return hipGetLastError();
+    return launch_select_scan_scatter(n, bits, idx, idx_cap, count_out, scratch, s);
 }
 
 }  // namespace krk

@@ -73,6 +73,26 @@ class DirCAS:
                 dirnames[:] = []
         return sorted(out)
 
+    def Listing(self):
+        """The cache as a castore.Listing: ListNames() with the columns cleanup needs -- mtime and
+        size from stat, the last access time from the _last_access_time sidecar beside `data`
+        (metadata.LastAccessTime; KRK_NO_TIME where there is none)."""
+        from . import castore
+        names = self.ListNames()
+        mtime, size, atime = [], [], []
+        for name in names:
+            st = self.GetCacheFileStat(name)
+            mtime.append(st.st_mtime_ns)
+            size.append(st.st_size)
+            try:
+                with open(os.path.join(self._dir(name), castore.LastAccessTime.Suffix), "rb") as f:
+                    lat = castore.LastAccessTime()
+                    lat.Deserialize(f.read())
+                atime.append(lat.Time * 1_000_000_000)
+            except FileNotFoundError:
+                atime.append(castore.KRK_NO_TIME)
+        return castore.Listing(names, mtime_ns=mtime, size=size, atime_ns=atime)
+
     def GetCacheFileStat(self, hex_: str) -> os.stat_result:
         return os.stat(os.path.join(self._dir(hex_), "data"))
 

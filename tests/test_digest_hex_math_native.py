@@ -1,0 +1,19 @@
+"""tests/native/digest_hex_math_main.cpp: the digest hex codec's and the expiry rule's host
+arithmetic (kraken_amd/csrc/digest_hex_math.hpp, what krk_digest_parse_hex, krk_digest_format_hex,
+krk_expiry_bits and krk_cleanup_plan run and digest_hex.hip equals) as a stand-alone CPU program
+(its own main, nothing of the library linked) built with AddressSanitizer and
+UndefinedBehaviorSanitizer and run directly."""
+import os
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_digest_hex_math_under_asan_ubsan(tmp_path):
+    src = os.path.join(ROOT, "tests", "native", "digest_hex_math_main.cpp")
+    exe = str(tmp_path / "digest_hex_math_san")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=all", "-o", exe, src])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert " 0 mismatches" in r.stdout and "runtime error" not in r.stderr, r.stdout + r.stderr
