@@ -225,6 +225,76 @@ int krk_verify_files(const krk_file_blob* files, uint64_t n_files, const uint32_
                      const uint8_t* expected_digests, uint64_t* bits_host, uint32_t* n_bad_host,
                      uint8_t* digest_ok_host);
 
+/* ------------------------------------------- piece request rounds
+ * What to ask the peers for next: the availability counts numPeersByPiece
+ * (lib/torrent/scheduler/dispatch/dispatcher.go:257-284, :495) and
+ * piecerequest.Manager.ReservePieces (piecerequest/manager.go:101-137) as bit-matrix work over
+ * the bitset layout above.  One torrent of N pieces (N < 2^32), W = krk_bitfield_words(N), P peers
+ * in a fixed order, a pipeline limit L (1 <= L <= KRK_PR_MAX_LIMIT):
+ *   counts[i] = the peers whose bitfield has bit i set (the column sum of the peers' rows).
+ *   For p = 0 .. P-1:  q = max(quota_p, 0);
+ *     cand   = bits_p & ~have & ~blocked_p & ~taken;
+ *     picks_p = the min(q, |cand|) candidates with the smallest (key(i), i), ascending in that pair;
+ *     taken |= picks_p, unless KRK_PR_ALLOW_DUPLICATES (then taken stays empty).
+ *   key(i) = counts[i]                                          KRK_PR_RAREST_FIRST
+ *            splitmix64(seed ^ ((uint64)p << 32 | i)) >> 32     KRK_PR_SAMPLE
+ * with splitmix64(x): z = x + 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;
+ * z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^ z >> 31.  KRK_PR_SAMPLE is the reference's default
+ * policy (default_policy.go:33-66, a uniform sample of `limit` valid candidates) made
+ * reproducible from a seed.  blocked_p is validRequest (manager.go:224-236) as a bitset: outside
+ * endgame the pieces with a pending, unexpired request to any peer, in endgame those pending to
+ * p itself.  A round with one positive quota is ReservePieces for that peer; with several it is
+ * ReservePieces called peer after peer at one clock instant (`taken` is the pending set growing).
+ * The one deliberate difference is tie order: equal keys go to the LOWER PIECE INDEX, where the
+ * reference's heap (rarest_first_policy.go:38-44) leaves them to container/heap's sift order; the
+ * sequence of counts popped is the same.  Tail bits past N of any row are ignored: never counted,
+ * never picked.
+ *
+ * Every output element is stored by the call, the caller pre-zeroes nothing: n_picked[p],
+ * picks[p * limit + j] (0xFFFFFFFF for j >= n_picked[p]), and counts when asked for.
+ * KRK_EINVAL, refused before any output is touched: n_pieces >= 2^32, a quota above the limit
+ * (host forms; the device form cannot read quota_dev before the launch and reads such a quota
+ * as the limit), a limit outside [1, KRK_PR_MAX_LIMIT], an unknown policy or flag bit, a NULL
+ * that is not nullable. */
+#define KRK_PR_MAX_LIMIT 16u
+#define KRK_PR_RAREST_FIRST 0u
+#define KRK_PR_SAMPLE 1u
+#define KRK_PR_ALLOW_DUPLICATES 0x100u
+#define KRK_PR_NONE 0xFFFFFFFFu
+typedef struct {
+    uint64_t n_pieces;    /* < 2^32 */
+    uint32_t n_peers;
+    uint32_t flags;       /* policy | KRK_PR_ALLOW_DUPLICATES */
+    uint64_t seed;        /* KRK_PR_SAMPLE only */
+    uint64_t bits_off;    /* first word of its rows in `bits`: have, then (bits_p, blocked_p) a peer */
+    uint64_t peer_off;    /* first peer in quota / n_picked / picks (picks row = peer * limit) */
+    uint64_t piece_off;   /* first piece in counts_out */
+} krk_request_torrent;
+/* counts_out[i], i < n_pieces, from n_peers rows of krk_bitfield_words(n_pieces) words back to
+ * back.  No device. */
+int krk_piece_availability(const uint64_t* peer_bits, uint32_t n_peers, uint64_t n_pieces, uint32_t* counts_out);
+/* selectPieces with `valid` passed as a bitset: the min(max(q, 0), |cand & ~blocked|) smallest
+ * (key(i), i) of one peer (`peer` enters KRK_PR_SAMPLE's key).  picks_out holds max(q, 0)
+ * entries, those from *n_out on 0xFFFFFFFF; q > KRK_PR_MAX_LIMIT is KRK_EINVAL.  blocked is
+ * nullable, counts is nullable under KRK_PR_SAMPLE.  No device. */
+int krk_piece_select(const uint64_t* cand, const uint64_t* blocked, const uint32_t* counts, uint64_t n_pieces,
+                     int32_t q, uint32_t flags, uint64_t seed, uint32_t peer, uint32_t* picks_out,
+                     uint32_t* n_out);
+/* The whole round of n_torrents torrents on the host.  counts_out is nullable.  The regions the
+ * torrents name in one array must not overlap. */
+int krk_piece_request_round(const krk_request_torrent* torrents, uint64_t n_torrents, const uint64_t* bits,
+                            const int32_t* quota, uint32_t limit, uint32_t* counts_out, uint32_t* picks_out,
+                            uint32_t* n_picked_out);
+/* The same on the device (piece_request.hip), bit for bit; asynchronous on `stream`: one launch
+ * for the counts and one for the rounds, one workgroup a torrent.  bits_dev, quota_dev and the
+ * outputs are device memory or page-locked host memory (krk_host_alloc), bits_dev 8-byte and the
+ * others 4-byte aligned: anything else is KRK_EINVAL before anything is launched.  torrents_host
+ * is copied into the library's staging before the call returns.  n_torrents == 0 is KRK_OK;
+ * KRK_ENODEV without a gfx950 device: there is no fall-back to the host form. */
+int krk_piece_request_round_dev(const krk_request_torrent* torrents_host, uint64_t n_torrents,
+                                const uint64_t* bits_dev, const int32_t* quota_dev, uint32_t limit,
+                                uint32_t* counts_out, uint32_t* picks_out, uint32_t* n_picked_out, void* stream);
+
 /* ------------------------------------------- re-piece stored MetaInfo, no blob read
  * The piece sums of a stored MetaInfo at a COARSER piece length, from the stored sums alone:
  * what a changed piece-length table (lib/metainfogen/config.go:48-80) asks of every

@@ -247,6 +247,12 @@ int krk_metainfo_json_scan_geometry(uint64_t* counts_per_pass, uint64_t* max_wor
  * krk_digest_parse_hex_dev / krk_digest_format_hex_dev takes, for the tests that pin their edges.
  * No device. */
 int krk_digest_hex_geometry(uint64_t* names_per_workgroup);
+/* The shape of piece_request.hip as built (kernel name "piece_request"): the pieces one workgroup
+ * pass of the selection scan covers, the thread stride inside it (one piece a thread; also the
+ * pieces of one count unit) and the count units a launch has workgroups for at the most (with
+ * more, the workgroups stride) -- for the tests that pin krk_piece_request_round_dev's edges.
+ * No device. */
+int krk_piece_request_geometry(uint64_t* pieces_per_pass, uint64_t* thread_stride, uint64_t* max_count_workgroups);
 
 /* ------------------------------------------------------- SHA-256 plans
  * Lanes per stream (1, 2 or 8) the library uses for a batch of n_streams streams on

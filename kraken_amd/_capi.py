@@ -18,6 +18,7 @@ INTERNAL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "kraken_h
 KRK_OK, KRK_EINVAL, KRK_EHIP, KRK_ENOMEM, KRK_ENODEV, KRK_ERANGE, KRK_EHEX, KRK_EIO, KRK_EFORMAT = 0, -1, -2, -3, -4, -5, -6, -7, -8
 KRK_PLACE_AUTO, KRK_PLACE_HOST, KRK_PLACE_GPU = 0, 1, 2
 KRK_OFFLOAD_AUTO = -1
+KRK_PR_MAX_LIMIT, KRK_PR_RAREST_FIRST, KRK_PR_SAMPLE, KRK_PR_ALLOW_DUPLICATES, KRK_PR_NONE = 16, 0, 1, 0x100, 0xFFFFFFFF
 
 
 class KrakenError(RuntimeError):
@@ -49,6 +50,11 @@ class krk_metainfo_json_blob(C.Structure):
 class krk_metainfo_json_span(C.Structure):
     _fields_ = [("text_off", C.c_uint64), ("text_len", C.c_uint64), ("sums_off", C.c_uint64),
                 ("expect_n", C.c_uint64)]
+
+
+class krk_request_torrent(C.Structure):
+    _fields_ = [("n_pieces", C.c_uint64), ("n_peers", C.c_uint32), ("flags", C.c_uint32), ("seed", C.c_uint64),
+                ("bits_off", C.c_uint64), ("peer_off", C.c_uint64), ("piece_off", C.c_uint64)]
 
 
 class krk_chunk(C.Structure):
@@ -114,6 +120,14 @@ def _load() -> C.CDLL:
         "krk_piece_bitfield": (i, [u32p, u32p, C.c_uint64, u64p, u32p]),
         "krk_verify_batch_dev": (i, [blobp, C.c_uint64, u32p, u8p, vp, vp, vp, vp]),
         "krk_verify_files": (i, [C.POINTER(krk_file_blob), C.c_uint64, u32p, u8p, u64p, u32p, u8p]),
+        "krk_piece_availability": (i, [u64p, C.c_uint32, C.c_uint64, u32p]),
+        "krk_piece_select": (i, [u64p, u64p, u32p, C.c_uint64, C.c_int32, C.c_uint32, C.c_uint64, C.c_uint32, u32p,
+                                 u32p]),
+        "krk_piece_request_round": (i, [C.POINTER(krk_request_torrent), C.c_uint64, u64p, i32p, C.c_uint32, u32p, u32p,
+                                        u32p]),
+        "krk_piece_request_round_dev": (i, [C.POINTER(krk_request_torrent), C.c_uint64, vp, vp, C.c_uint32, vp, vp, vp,
+                                            vp]),
+        "krk_piece_request_geometry": (i, [u64p, u64p, u64p]),
         "krk_repiece_sums": (i, [u32p, C.c_uint64, C.c_int64, C.c_int64, C.c_int64, u32p, C.c_uint64]),
         "krk_repiece_batch": (i, [C.POINTER(krk_repiece_blob), C.c_uint64, u32p, u32p]),
         "krk_repiece_batch_dev": (i, [C.POINTER(krk_repiece_blob), C.c_uint64, vp, vp, vp]),

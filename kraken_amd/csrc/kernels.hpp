@@ -355,6 +355,35 @@ hipError_t launch_cleanup_plan(const uint8_t* names, const uint64_t* off, uint64
                                int64_t ttl, const uint32_t* mask, int invert, uint64_t* bits, uint64_t* valid,
                                uint64_t* idx, uint64_t idx_cap, uint64_t* count_out, void* scratch, hipStream_t s);
 
+// ---------------------------------------------------------------- piece requests
+// One torrent of a request round (piece_request.hip, piece_request_math.hpp): its rows are
+// bits[bits_off, + (1 + 2 n_peers) W), W = ceil(n_pieces / 64): have, then (bits_p, blocked_p) a
+// peer; its peers are quota / n_picked [peer_off, + n_peers) and picks rows of `limit` from
+// peer_off * limit; its counts are counts[piece_off, + n_pieces), its taken row the W words from
+// taken[taken_off].  first_unit ascends with the torrent index (torrent t's
+// ceil(n_pieces / kPrG) count units follow torrent t-1's) and tors[0].first_unit == 0.
+struct alignas(16) PrTorrent {
+    uint64_t n_pieces;  // < 2^32
+    uint64_t bits_off;
+    uint64_t peer_off;
+    uint64_t piece_off;
+    uint64_t seed;
+    uint64_t taken_off;
+    uint64_t first_unit;
+    uint32_t n_peers;
+    uint32_t flags;  // pr::kRarestFirst / pr::kSample | pr::kAllowDuplicates
+};
+static_assert(sizeof(PrTorrent) == 64, "PrTorrent layout");
+constexpr uint32_t kPrG = 256;      // a count unit, and the thread stride of both kernels: one piece a thread
+constexpr uint32_t kPrPass = 4096;  // the pieces one step of the selection scan covers: 16 strides
+constexpr uint32_t kPrMaxBlocks = 1u << 10;  // count units beyond: the workgroups stride
+// counts (nullable: no count launch; then no torrent may be rarest-first): every
+// counts[piece_off + i] stored.  Then one workgroup a torrent runs its peers in order: every
+// n_picked and picks entry stored; a quota above `limit` is read as `limit`.
+hipError_t launch_piece_request(const PrTorrent* tors, uint64_t n_tors, uint64_t n_units, const uint64_t* bits,
+                                const int32_t* quota, uint32_t limit, uint32_t* counts, uint64_t* taken,
+                                uint32_t* picks, uint32_t* n_picked, hipStream_t s);
+
 // ---------------------------------------------------------------- synthetic data
 // One synthetic chunk: bytes [offset, offset + n) of the blob whose stream seed is `seed`.
 struct SynthChunk {

@@ -7,7 +7,8 @@ import os
 
 import numpy as np
 
-from ._capi import check, krk_blob, krk_file_blob, krk_chunk, krk_launch_rec, krk_nodes, krk_planner_rates, lib
+from ._capi import (check, krk_blob, krk_file_blob, krk_chunk, krk_launch_rec, krk_nodes, krk_planner_rates,
+                    krk_request_torrent, lib)
 
 ALIGN = 256  # every blob starts 256-byte aligned in the arena
 
@@ -782,6 +783,143 @@ def ring_locations_u8_dev(digests_dev: DeviceBuffer, n: int, labels, healthy, ma
     check(lib.krk_ring_locations_u8_dev(digests_dev.ptr, n, C.byref(s), h.ctypes.data_as(C.POINTER(C.c_uint8)),
                                          max_replica, locs_dev.ptr, counts_dev.ptr, stream))
     del keep
+
+
+# ------------------------------------------------------------------ piece request rounds
+PR_MAX_LIMIT, PR_RAREST_FIRST, PR_SAMPLE, PR_ALLOW_DUPLICATES, PR_NONE = 16, 0, 1, 0x100, 0xFFFFFFFF
+
+
+class RequestBatch:
+    """The layout of one request round over a batch of torrents, packed back to back: torrent t's
+    rows (have, then (bits_p, blocked_p) a peer, krk_bitfield_words(n_pieces) words each) start at
+    word .bits_off[t], its peers at .peer_off[t], its counts at .piece_off[t]; .structs is the
+    krk_request_torrent array the round calls take."""
+
+    def __init__(self, n_pieces, n_peers, flags=PR_RAREST_FIRST, seeds=0):
+        n = np.asarray(n_pieces, dtype=np.uint64).reshape(-1)
+        k = n.size
+        self.n_pieces = n
+        self.n_peers = np.broadcast_to(np.asarray(n_peers, dtype=np.uint32), (k,)).copy()
+        self.flags = np.broadcast_to(np.asarray(flags, dtype=np.uint32), (k,)).copy()
+        self.seeds = np.broadcast_to(np.asarray(seeds, dtype=np.uint64), (k,)).copy()
+        self.words = (n + np.uint64(63)) // np.uint64(64)
+        rows = self.words * (np.uint64(1) + np.uint64(2) * self.n_peers.astype(np.uint64))
+        self.bits_off, self.peer_off, self.piece_off = (np.zeros(k + 1, dtype=np.uint64) for _ in range(3))
+        self.bits_off[1:], self.peer_off[1:], self.piece_off[1:] = np.cumsum(rows), np.cumsum(self.n_peers), np.cumsum(n)
+        self.total_words, self.total_peers, self.total_pieces = (int(o[-1]) for o in
+                                                                 (self.bits_off, self.peer_off, self.piece_off))
+        self.structs = (krk_request_torrent * max(k, 1))()
+        for t in range(k):
+            self.structs[t] = krk_request_torrent(int(n[t]), int(self.n_peers[t]), int(self.flags[t]), int(self.seeds[t]),
+                                                  int(self.bits_off[t]), int(self.peer_off[t]), int(self.piece_off[t]))
+
+    def __len__(self):
+        return int(self.n_pieces.size)
+
+    def rows(self, bits: np.ndarray, t: int) -> np.ndarray:
+        """Torrent t's rows as a (1 + 2 n_peers, words) view of the batch's `bits` array."""
+        a, b = int(self.bits_off[t]), int(self.bits_off[t + 1])
+        return bits[a:b].reshape(1 + 2 * int(self.n_peers[t]), int(self.words[t]))
+
+
+class RequestOutputs:
+    """The outputs of piece_request_round_dev over a RequestBatch, in device memory or
+    (pinned=True) in page-locked host memory the kernels write over PCIe: .counts (uint32 a piece;
+    only with counts), .picks (uint32, `limit` a peer), .n_picked (uint32 a peer)."""
+
+    def __init__(self, batch: RequestBatch, limit: int, counts: bool = False, pinned: bool = False):
+        self.pieces, self.peers, self.limit, self.pinned = batch.total_pieces, batch.total_peers, int(limit), pinned
+        sizes = (self.pieces if counts else None, self.peers * self.limit, self.peers)
+        make = (lambda k: PinnedArray((max(k, 1),), np.uint32)) if pinned else (lambda k: DeviceBuffer(max(k, 1) * 4))
+        self.counts, self.picks, self.n_picked = (None if k is None else make(k) for k in sizes)
+
+    def fill(self, byte: int):
+        """Every output byte set to `byte` (tests: the call must overwrite all of it)."""
+        for b in (self.counts, self.picks, self.n_picked):
+            if b is None:
+                continue
+            if self.pinned:
+                b.a.view(np.uint8)[:] = byte
+            else:
+                b.from_host(np.full(b.nbytes, byte, dtype=np.uint8))
+
+    def to_host(self):
+        """(counts or None, picks (peers, limit), n_picked) as numpy arrays, once the call's stream has run."""
+        def get(b, k):
+            if b is None:
+                return None
+            return b.a[:k].copy() if self.pinned else b.to_host(np.uint32, k)
+        return get(self.counts, self.pieces), get(self.picks, self.peers * self.limit).reshape(self.peers, self.limit), \
+            get(self.n_picked, self.peers)
+
+
+def _p(a, t):
+    return a.ctypes.data_as(C.POINTER(t)) if a is not None and a.size else None
+
+
+def piece_availability(peer_bits, n_pieces: int) -> np.ndarray:
+    """krk_piece_availability: numPeersByPiece as the column sum of the peers' bitfield rows
+    ((n_peers, words) uint64).  Pure host code."""
+    words = int(lib.krk_bitfield_words(int(n_pieces)))
+    b = np.ascontiguousarray(peer_bits, dtype=np.uint64).reshape(-1, words) if words else np.zeros((len(peer_bits), 0), np.uint64)
+    counts = np.zeros(int(n_pieces), dtype=np.uint32)
+    check(lib.krk_piece_availability(_p(b, C.c_uint64), b.shape[0], int(n_pieces), _p(counts, C.c_uint32)))
+    return counts
+
+
+def piece_select(cand, blocked, counts, n_pieces: int, q: int, flags: int = PR_RAREST_FIRST, seed: int = 0,
+                 peer: int = 0) -> np.ndarray:
+    """krk_piece_select: the min(q, candidates) pieces of cand & ~blocked with the smallest
+    (key, index), in that order.  Pure host code."""
+    c = np.ascontiguousarray(cand, dtype=np.uint64)
+    b = None if blocked is None else np.ascontiguousarray(blocked, dtype=np.uint64)
+    k = None if counts is None else np.ascontiguousarray(counts, dtype=np.uint32)
+    picks = np.zeros(max(int(q), 0), dtype=np.uint32)
+    m = C.c_uint32()
+    check(lib.krk_piece_select(_p(c, C.c_uint64), _p(b, C.c_uint64), _p(k, C.c_uint32), int(n_pieces), int(q), int(flags),
+                               int(seed), int(peer), _p(picks, C.c_uint32), C.byref(m)))
+    return picks[:m.value]
+
+
+def piece_request_round(batch: RequestBatch, bits, quota, limit: int, counts: bool = False):
+    """krk_piece_request_round: the whole round on the host.  bits: uint64, the batch's layout;
+    quota: int32 a peer.  Returns (counts or None, picks (peers, limit), n_picked)."""
+    b = np.ascontiguousarray(bits, dtype=np.uint64)
+    q = np.ascontiguousarray(quota, dtype=np.int32)
+    if b.size < batch.total_words or q.size < batch.total_peers:
+        raise ValueError(f"piece_request_round: {b.size} words and {q.size} quotas for a batch of "
+                         f"{batch.total_words} and {batch.total_peers}")
+    cnt = np.zeros(batch.total_pieces, dtype=np.uint32) if counts else None
+    picks = np.zeros((batch.total_peers, int(limit)), dtype=np.uint32)
+    n_picked = np.zeros(batch.total_peers, dtype=np.uint32)
+    check(lib.krk_piece_request_round(batch.structs, len(batch), _p(b, C.c_uint64), _p(q, C.c_int32), int(limit),
+                                      _p(cnt, C.c_uint32) if counts else None, _p(picks, C.c_uint32),
+                                      _p(n_picked, C.c_uint32)))
+    return cnt, picks, n_picked
+
+
+def piece_request_round_dev(batch: RequestBatch, bits_dev, quota_dev, limit: int, out: RequestOutputs | None = None,
+                            counts: bool = False, stream=None):
+    """krk_piece_request_round_dev: the round in one call on the device.  bits_dev / quota_dev:
+    DeviceBuffer or PinnedArray in the batch's layout.  out: RequestOutputs to fill asynchronously
+    on `stream` (returned); None: (counts or None, picks, n_picked), returned once the stream has
+    run the call."""
+    dst = RequestOutputs(batch, limit, counts=counts, pinned=True) if out is None else out
+    check(lib.krk_piece_request_round_dev(batch.structs, len(batch), bits_dev.ptr, quota_dev.ptr, int(limit),
+                                          dst.counts.ptr if dst.counts is not None else None, dst.picks.ptr,
+                                          dst.n_picked.ptr, stream))
+    if out is not None:
+        return out
+    check(lib.krk_stream_sync(stream))
+    return dst.to_host()
+
+
+def piece_request_geometry():
+    """(pieces one workgroup pass of the selection scan covers, the thread stride inside it, count
+    workgroups a launch has at the most)."""
+    g, t, m = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    check(lib.krk_piece_request_geometry(C.byref(g), C.byref(t), C.byref(m)))
+    return int(g.value), int(t.value), int(m.value)
 
 
 class KernelTimer:
