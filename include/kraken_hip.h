@@ -295,6 +295,68 @@ int krk_piece_request_round_dev(const krk_request_torrent* torrents_host, uint64
                                 const uint64_t* bits_dev, const int32_t* quota_dev, uint32_t limit,
                                 uint32_t* counts_out, uint32_t* picks_out, uint32_t* n_picked_out, void* stream);
 
+/* ------------------------------------------- resend rounds
+ * Where the failed piece requests go next: Dispatcher.resendFailedPieceRequests
+ * (lib/torrent/scheduler/dispatch/dispatcher.go:401-434) for every torrent of a batch, over the
+ * rows of a request round.  A torrent is its krk_request_torrent, unchanged (piece_off, the seed
+ * and the policy bits of flags are not read -- one candidate needs no choice --
+ * KRK_PR_ALLOW_DUPLICATES is), and a list of F failed requests that ascends by piece, the
+ * entries of one piece adjacent and in the caller's order:
+ *   left_p = max(quota_p, 0)
+ *   for f = 0 .. F-1, i = piece_f:
+ *     target_f = KRK_PR_NONE
+ *     for p = 0 .. P-1:                      the first eligible peer wins
+ *       skip if status_f is EXPIRED or INVALID and p == peer_f      (dispatcher.go:412-416)
+ *       skip unless bit i of bits_p and not bit i of have           (:418-420)
+ *       skip if left_p == 0                                         (requestQuota, manager.go:110-113)
+ *       skip if bit i of blocked_p                                  (validRequest, :224-236)
+ *       skip if an earlier entry of this call with the same piece was resent
+ *            to p (KRK_PR_ALLOW_DUPLICATES) / to any peer (otherwise)
+ *       target_f = p; left_p -= 1; break
+ * The last skip is the pending set growing inside the call: after ReservePieces(p, {i}) the new
+ * request blocks p itself and, outside endgame, everybody.  quota_p is requestQuota(p), any int32.
+ * Two deliberate differences from the reference.  It walks the failed requests in Go map order
+ * and the peers in sync.Map order, both random; here the list order is the caller's (ascending
+ * piece) and the peers go in index order.  Its `sent` counter is shadowed and never incremented
+ * (:408, :422); n_resent_out is the count it meant to keep.
+ *
+ * Every output element is stored by the call, the caller pre-zeroes nothing:
+ * target_out[failed_off + f] (the peer's index or KRK_PR_NONE), quota_left_out[peer_off + p]
+ * (left_p after the torrent's list; nullable) and n_resent_out[t].  KRK_EINVAL, refused before
+ * any output is touched: n_pieces >= 2^32, a piece >= n_pieces, a peer that is neither < n_peers
+ * nor KRK_PR_NONE, a status outside 1..3, a list that does not ascend by piece, an unknown flag
+ * bit, a NULL that is not nullable.  KRK_ERANGE: a list of 2^32 entries or more.  The regions the
+ * torrents name in one array must not overlap. */
+#define KRK_PR_EXPIRED 1u /* piecerequest.StatusExpired / StatusUnsent / StatusInvalid */
+#define KRK_PR_UNSENT 2u
+#define KRK_PR_INVALID 3u
+typedef struct {
+    uint32_t piece;
+    uint32_t peer;   /* index among the torrent's peers, or KRK_PR_NONE: the peer has left (ClearPeer
+                        ejects only the first entry a piece, manager.go:188-196, so such entries survive) */
+    uint32_t status; /* KRK_PR_EXPIRED, KRK_PR_UNSENT, KRK_PR_INVALID */
+} krk_failed_request;
+typedef struct {
+    uint64_t failed_off; /* first entry in `failed` and in target_out */
+    uint64_t n_failed;
+} krk_resend_torrent;    /* parallel to torrents[] */
+/* The whole round of n_torrents torrents on the host.  No device. */
+int krk_piece_resend_round(const krk_request_torrent* torrents, const krk_resend_torrent* resends,
+                           uint64_t n_torrents, const uint64_t* bits, const int32_t* quota,
+                           const krk_failed_request* failed, uint32_t* target_out, int32_t* quota_left_out,
+                           uint32_t* n_resent_out);
+/* The same on the device (piece_resend.hip), bit for bit; asynchronous on `stream`: one launch,
+ * one workgroup a torrent.  bits_dev, quota_dev and the outputs are device memory or page-locked
+ * host memory (krk_host_alloc), bits_dev 8-byte and the others 4-byte aligned: anything else is
+ * KRK_EINVAL before anything is launched.  torrents_host, resends_host and failed_host are host
+ * memory: the lists are checked as above, and all three are copied into the library's staging,
+ * before the call returns.  n_torrents == 0 is KRK_OK; KRK_ENODEV without a gfx950 device: there
+ * is no fall-back to the host form. */
+int krk_piece_resend_round_dev(const krk_request_torrent* torrents_host, const krk_resend_torrent* resends_host,
+                               uint64_t n_torrents, const uint64_t* bits_dev, const int32_t* quota_dev,
+                               const krk_failed_request* failed_host, uint32_t* target_out,
+                               int32_t* quota_left_out, uint32_t* n_resent_out, void* stream);
+
 /* ------------------------------------------- re-piece stored MetaInfo, no blob read
  * The piece sums of a stored MetaInfo at a COARSER piece length, from the stored sums alone:
  * what a changed piece-length table (lib/metainfogen/config.go:48-80) asks of every

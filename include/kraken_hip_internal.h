@@ -253,6 +253,11 @@ int krk_digest_hex_geometry(uint64_t* names_per_workgroup);
  * more, the workgroups stride) -- for the tests that pin krk_piece_request_round_dev's edges.
  * No device. */
 int krk_piece_request_geometry(uint64_t* pieces_per_pass, uint64_t* thread_stride, uint64_t* max_count_workgroups);
+/* The shape of piece_resend.hip as built (kernel name "piece_resend"): the peers one workgroup
+ * pass over a failed entry's peers covers, one peer a thread (a torrent with more peers takes
+ * further passes, whose state is in memory and not in registers) -- for the tests that pin
+ * krk_piece_resend_round_dev's edges.  No device. */
+int krk_piece_resend_geometry(uint64_t* peers_per_pass);
 
 /* ------------------------------------------------------- SHA-256 plans
  * Lanes per stream (1, 2 or 8) the library uses for a batch of n_streams streams on

@@ -19,6 +19,7 @@ KRK_OK, KRK_EINVAL, KRK_EHIP, KRK_ENOMEM, KRK_ENODEV, KRK_ERANGE, KRK_EHEX, KRK_
 KRK_PLACE_AUTO, KRK_PLACE_HOST, KRK_PLACE_GPU = 0, 1, 2
 KRK_OFFLOAD_AUTO = -1
 KRK_PR_MAX_LIMIT, KRK_PR_RAREST_FIRST, KRK_PR_SAMPLE, KRK_PR_ALLOW_DUPLICATES, KRK_PR_NONE = 16, 0, 1, 0x100, 0xFFFFFFFF
+KRK_PR_EXPIRED, KRK_PR_UNSENT, KRK_PR_INVALID = 1, 2, 3
 
 
 class KrakenError(RuntimeError):
@@ -55,6 +56,14 @@ class krk_metainfo_json_span(C.Structure):
 class krk_request_torrent(C.Structure):
     _fields_ = [("n_pieces", C.c_uint64), ("n_peers", C.c_uint32), ("flags", C.c_uint32), ("seed", C.c_uint64),
                 ("bits_off", C.c_uint64), ("peer_off", C.c_uint64), ("piece_off", C.c_uint64)]
+
+
+class krk_failed_request(C.Structure):
+    _fields_ = [("piece", C.c_uint32), ("peer", C.c_uint32), ("status", C.c_uint32)]
+
+
+class krk_resend_torrent(C.Structure):
+    _fields_ = [("failed_off", C.c_uint64), ("n_failed", C.c_uint64)]
 
 
 class krk_chunk(C.Structure):
@@ -128,6 +137,11 @@ def _load() -> C.CDLL:
         "krk_piece_request_round_dev": (i, [C.POINTER(krk_request_torrent), C.c_uint64, vp, vp, C.c_uint32, vp, vp, vp,
                                             vp]),
         "krk_piece_request_geometry": (i, [u64p, u64p, u64p]),
+        "krk_piece_resend_round": (i, [C.POINTER(krk_request_torrent), C.POINTER(krk_resend_torrent), C.c_uint64, u64p,
+                                       i32p, C.POINTER(krk_failed_request), u32p, i32p, u32p]),
+        "krk_piece_resend_round_dev": (i, [C.POINTER(krk_request_torrent), C.POINTER(krk_resend_torrent), C.c_uint64, vp,
+                                           vp, C.POINTER(krk_failed_request), vp, vp, vp, vp]),
+        "krk_piece_resend_geometry": (i, [u64p]),
         "krk_repiece_sums": (i, [u32p, C.c_uint64, C.c_int64, C.c_int64, C.c_int64, u32p, C.c_uint64]),
         "krk_repiece_batch": (i, [C.POINTER(krk_repiece_blob), C.c_uint64, u32p, u32p]),
         "krk_repiece_batch_dev": (i, [C.POINTER(krk_repiece_blob), C.c_uint64, vp, vp, vp]),

@@ -384,6 +384,35 @@ hipError_t launch_piece_request(const PrTorrent* tors, uint64_t n_tors, uint64_t
                                 const int32_t* quota, uint32_t limit, uint32_t* counts, uint64_t* taken,
                                 uint32_t* picks, uint32_t* n_picked, hipStream_t s);
 
+// One torrent of a resend round (piece_resend.hip, piece_resend_math.hpp): its rows as a request
+// round's, its quotas quota[peer_off, + n_peers), its quota left left[left_off, + n_peers), its
+// marks mark[mark_off, + n_peers) (scratch; touched from peer kRsS on, and only with
+// allow-duplicates), its n_failed entries failed[list_off ..] with their targets at
+// target[failed_off ..].  n_resent is indexed by the torrent.
+namespace rs {
+struct Failed;
+}
+struct alignas(16) RsTorrent {
+    uint64_t n_pieces;  // < 2^32
+    uint64_t bits_off;
+    uint64_t peer_off;
+    uint64_t left_off;
+    uint64_t mark_off;
+    uint64_t list_off;
+    uint64_t failed_off;
+    uint64_t n_failed;
+    uint32_t n_peers;
+    uint32_t flags;  // pr::kAllowDuplicates is read
+    uint64_t pad;
+};
+static_assert(sizeof(RsTorrent) == 80, "RsTorrent layout");
+constexpr uint32_t kRsS = 256;  // the peers one pass over a failed entry's peers covers: one peer a thread
+// One workgroup a torrent runs its failed entries in order: every target, left and n_resent
+// entry stored.  The lists are valid (rs::list_error).
+hipError_t launch_piece_resend(const RsTorrent* tors, uint64_t n_tors, const uint64_t* bits, const int32_t* quota,
+                               const rs::Failed* failed, int32_t* left, uint32_t* mark, uint32_t* target,
+                               uint32_t* n_resent, hipStream_t s);
+
 // ---------------------------------------------------------------- synthetic data
 // One synthetic chunk: bytes [offset, offset + n) of the blob whose stream seed is `seed`.
 struct SynthChunk {

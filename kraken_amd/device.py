@@ -8,7 +8,7 @@ import os
 import numpy as np
 
 from ._capi import (check, krk_blob, krk_file_blob, krk_chunk, krk_launch_rec, krk_nodes, krk_planner_rates,
-                    krk_request_torrent, lib)
+                    krk_request_torrent, krk_resend_torrent, krk_failed_request, lib)
 
 ALIGN = 256  # every blob starts 256-byte aligned in the arena
 
@@ -920,6 +920,111 @@ def piece_request_geometry():
     g, t, m = C.c_uint64(), C.c_uint64(), C.c_uint64()
     check(lib.krk_piece_request_geometry(C.byref(g), C.byref(t), C.byref(m)))
     return int(g.value), int(t.value), int(m.value)
+
+
+PR_EXPIRED, PR_UNSENT, PR_INVALID = 1, 2, 3
+
+
+class ResendBatch:
+    """The failed requests of a resend round over a RequestBatch: one list of (piece, peer index or
+    PR_NONE, status) a torrent, ascending by piece, packed back to back.  Torrent t's entries (and
+    its targets) start at .failed_off[t]; .structs is the krk_resend_torrent array parallel to the
+    batch's, .failed the krk_failed_request array."""
+
+    def __init__(self, batch: RequestBatch, lists):
+        lists = [list(l) for l in lists]
+        if len(lists) != len(batch):
+            raise ValueError(f"ResendBatch: {len(lists)} lists for a batch of {len(batch)} torrents")
+        k = len(lists)
+        self.failed_off = np.zeros(k + 1, dtype=np.uint64)
+        self.failed_off[1:] = np.cumsum([len(l) for l in lists])
+        self.total_failed = int(self.failed_off[-1])
+        self.structs = (krk_resend_torrent * max(k, 1))()
+        self.failed = (krk_failed_request * max(self.total_failed, 1))()
+        j = 0
+        for t, l in enumerate(lists):
+            self.structs[t] = krk_resend_torrent(int(self.failed_off[t]), len(l))
+            for piece, peer, status in l:
+                self.failed[j] = krk_failed_request(int(piece), int(peer), int(status))
+                j += 1
+
+    def split(self, a: np.ndarray, t: int) -> np.ndarray:
+        """Torrent t's slice of an array with one element a failed request (the targets)."""
+        return a[int(self.failed_off[t]):int(self.failed_off[t + 1])]
+
+
+class ResendOutputs:
+    """The outputs of piece_resend_round_dev, in device memory or (pinned=True) in page-locked host
+    memory the kernel writes over PCIe: .target (uint32 a failed request), .quota_left (int32 a
+    peer; only with quota_left), .n_resent (uint32 a torrent)."""
+
+    def __init__(self, batch: RequestBatch, resend: ResendBatch, quota_left: bool = True, pinned: bool = False):
+        self.failed, self.peers, self.torrents, self.pinned = resend.total_failed, batch.total_peers, len(batch), pinned
+        make = (lambda k, t: PinnedArray((max(k, 1),), t)) if pinned else (lambda k, t: DeviceBuffer(max(k, 1) * 4))
+        self.target = make(self.failed, np.uint32)
+        self.quota_left = make(self.peers, np.int32) if quota_left else None
+        self.n_resent = make(self.torrents, np.uint32)
+
+    def fill(self, byte: int):
+        """Every output byte set to `byte` (tests: the call must overwrite all of it)."""
+        for b in (self.target, self.quota_left, self.n_resent):
+            if b is None:
+                continue
+            if self.pinned:
+                b.a.view(np.uint8)[:] = byte
+            else:
+                b.from_host(np.full(b.nbytes, byte, dtype=np.uint8))
+
+    def to_host(self):
+        """(target, quota_left or None, n_resent) as numpy arrays, once the call's stream has run."""
+        def get(b, k, t):
+            if b is None:
+                return None
+            return b.a[:k].copy() if self.pinned else b.to_host(t, k)
+        return get(self.target, self.failed, np.uint32), get(self.quota_left, self.peers, np.int32), \
+            get(self.n_resent, self.torrents, np.uint32)
+
+
+def piece_resend_round(batch: RequestBatch, resend: ResendBatch, bits, quota, quota_left: bool = True):
+    """krk_piece_resend_round: the whole resend round on the host.  bits: uint64, the batch's
+    layout; quota: int32 a peer.  Returns (target a failed request, quota_left a peer or None,
+    n_resent a torrent)."""
+    b = np.ascontiguousarray(bits, dtype=np.uint64)
+    q = np.ascontiguousarray(quota, dtype=np.int32)
+    if b.size < batch.total_words or q.size < batch.total_peers:
+        raise ValueError(f"piece_resend_round: {b.size} words and {q.size} quotas for a batch of "
+                         f"{batch.total_words} and {batch.total_peers}")
+    target = np.zeros(resend.total_failed, dtype=np.uint32)
+    left = np.zeros(batch.total_peers, dtype=np.int32) if quota_left else None
+    n_resent = np.zeros(len(batch), dtype=np.uint32)
+    check(lib.krk_piece_resend_round(batch.structs, resend.structs, len(batch), _p(b, C.c_uint64), _p(q, C.c_int32),
+                                     resend.failed, _p(target, C.c_uint32),
+                                     _p(left, C.c_int32) if quota_left else None, _p(n_resent, C.c_uint32)))
+    return target, left, n_resent
+
+
+def piece_resend_round_dev(batch: RequestBatch, resend: ResendBatch, bits_dev, quota_dev,
+                           out: ResendOutputs | None = None, quota_left: bool = True, stream=None):
+    """krk_piece_resend_round_dev: the resend round in one call on the device.  bits_dev /
+    quota_dev: DeviceBuffer or PinnedArray in the batch's layout (the rows a reserve round
+    uploaded serve as they are).  out: ResendOutputs to fill asynchronously on `stream` (returned);
+    None: (target, quota_left or None, n_resent), returned once the stream has run the call."""
+    dst = ResendOutputs(batch, resend, quota_left=quota_left, pinned=True) if out is None else out
+    check(lib.krk_piece_resend_round_dev(batch.structs, resend.structs, len(batch), bits_dev.ptr, quota_dev.ptr,
+                                         resend.failed, dst.target.ptr,
+                                         dst.quota_left.ptr if dst.quota_left is not None else None, dst.n_resent.ptr,
+                                         stream))
+    if out is not None:
+        return out
+    check(lib.krk_stream_sync(stream))
+    return dst.to_host()
+
+
+def piece_resend_geometry() -> int:
+    """The peers one workgroup pass over a failed request's peers covers (one peer a thread)."""
+    s = C.c_uint64()
+    check(lib.krk_piece_resend_geometry(C.byref(s)))
+    return int(s.value)
 
 
 class KernelTimer:

@@ -12,8 +12,13 @@ uniform sample (default_policy.go:33-66), drawn from a seed instead of Go's glob
 (dispatch/dispatcher.go:374-399) runs ReservePieces for one peer after every piece that arrives;
 a round runs it for every peer of every torrent at one clock instant, in one
 ``krk_piece_request_round`` call (placement "host") or one ``krk_piece_request_round_dev`` call
-(placement "gpu": one workgroup a torrent), and records the picks as pending.  Connections, the
-wire protocol and resendFailedPieceRequests' retries stay with the caller.
+(placement "gpu": one workgroup a torrent), and records the picks as pending.
+
+``ResendRound`` is ``Dispatcher.resendFailedPieceRequests`` (dispatch/dispatcher.go:401-434) batched
+the same way: every expired, unsent and invalid request of every torrent placed on the first peer
+that holds the piece, has quota left and may be asked (``krk_piece_resend_round`` /
+``krk_piece_resend_round_dev``, over the rows a reserve round uses), and recorded as pending there.
+Connections and the wire protocol stay with the caller.
 """
 from __future__ import annotations
 
@@ -222,6 +227,22 @@ class Dispatcher:
                                     self.n_pieces)
 
 
+def _round_inputs(ds, dups, flags, seeds):
+    """(RequestBatch, bits, quota) of one round over the dispatchers ds: a torrent's rows are have,
+    then (bitfield, blocked) a peer in the dispatcher's peer order; quota is requestQuota a peer."""
+    batch = D.RequestBatch([d.n_pieces for d in ds], [len(d.peers) for d in ds], flags, seeds)
+    bits = np.zeros(batch.total_words, dtype=np.uint64)
+    quota = np.zeros(batch.total_peers, dtype=np.int32)
+    for t, (d, dup) in enumerate(zip(ds, dups)):
+        rows = batch.rows(bits, t)
+        rows[0] = bitset_words(d.have)
+        for p, (peerID, b) in enumerate(d.peers.items()):
+            rows[1 + 2 * p] = bitset_words(b)
+            rows[2 + 2 * p] = d.manager.blocked(peerID, d.n_pieces, dup)
+            quota[int(batch.peer_off[t]) + p] = d.manager.requestQuota(peerID)
+    return batch, bits, quota
+
+
 def ReserveRound(dispatchers, placement: str = "host"):
     """ReservePieces for every peer of every dispatcher at one clock instant, in one call: the
     peers of a torrent in their order, each seeing the reservations of those before it (in endgame:
@@ -240,16 +261,7 @@ def ReserveRound(dispatchers, placement: str = "host"):
     dups = [d.endgame() for d in ds]
     flags = [d.manager.policy | (D.PR_ALLOW_DUPLICATES if dup else 0) for d, dup in zip(ds, dups)]
     seeds = [d.manager.next_seed() if d.manager.policy == D.PR_SAMPLE else 0 for d in ds]
-    batch = D.RequestBatch([d.n_pieces for d in ds], [len(d.peers) for d in ds], flags, seeds)
-    bits = np.zeros(batch.total_words, dtype=np.uint64)
-    quota = np.zeros(batch.total_peers, dtype=np.int32)
-    for t, (d, dup) in enumerate(zip(ds, dups)):
-        rows = batch.rows(bits, t)
-        rows[0] = bitset_words(d.have)
-        for p, (peerID, b) in enumerate(d.peers.items()):
-            rows[1 + 2 * p] = bitset_words(b)
-            rows[2 + 2 * p] = d.manager.blocked(peerID, d.n_pieces, dup)
-            quota[int(batch.peer_off[t]) + p] = d.manager.requestQuota(peerID)
+    batch, bits, quota = _round_inputs(ds, dups, flags, seeds)
     if placement == "host":
         _, picks, n_picked = D.piece_request_round(batch, bits, quota, limit)
     else:
@@ -264,5 +276,48 @@ def ReserveRound(dispatchers, placement: str = "host"):
             k = int(batch.peer_off[t]) + p
             got[peerID] = picks[k, :int(n_picked[k])].tolist()
             d.manager.record(peerID, got[peerID])
+        out.append(got)
+    return out
+
+
+def ResendRound(dispatchers, placement: str = "host"):
+    """resendFailedPieceRequests for every dispatcher at one clock instant, in one call: a
+    dispatcher's failed requests (expired, unsent, invalid) by piece and then by their position in
+    requests[piece], each to the first peer, in the dispatcher's peer order, that holds the piece,
+    has quota left and may be asked for it; an expired or invalid request never goes back to its
+    own peer.  Returns one [(Request, target peerID or None)] a dispatcher; the resent pieces are
+    pending on their targets in the dispatchers' managers afterwards.  No seed is drawn.  The
+    dispatchers need not share a pipeline limit.  placement "host": krk_piece_resend_round; "gpu":
+    krk_piece_resend_round_dev (an error without a device)."""
+    if placement not in ("host", "gpu"):
+        raise ValueError(f"ResendRound: placement {placement!r} is neither \"host\" nor \"gpu\"")
+    ds = list(dispatchers)
+    if not ds:
+        return []
+    failed = [sorted(d.manager.GetFailedRequests(), key=lambda r: r.Piece) for d in ds]  # stable: positions kept
+    dups = [d.endgame() for d in ds]
+    flags = [d.manager.policy | (D.PR_ALLOW_DUPLICATES if dup else 0) for d, dup in zip(ds, dups)]
+    batch, bits, quota = _round_inputs(ds, dups, flags, 0)
+    lists = []
+    for d, rs in zip(ds, failed):
+        index = {peerID: p for p, peerID in enumerate(d.peers)}
+        lists.append([(r.Piece, index.get(r.PeerID, D.PR_NONE), r.Status) for r in rs])
+    resend = D.ResendBatch(batch, lists)
+    if placement == "host":
+        target, _, _ = D.piece_resend_round(batch, resend, bits, quota, quota_left=False)
+    else:
+        bits_dev, quota_dev = D.DeviceBuffer(bits.nbytes), D.DeviceBuffer(quota.nbytes)
+        bits_dev.from_host(bits)
+        quota_dev.from_host(quota)
+        target, _, _ = D.piece_resend_round_dev(batch, resend, bits_dev, quota_dev, quota_left=False)
+    out = []
+    for t, (d, rs) in enumerate(zip(ds, failed)):
+        peers = list(d.peers)
+        got = []
+        for r, p in zip(rs, resend.split(target, t).tolist()):
+            peerID = None if p == D.PR_NONE else peers[p]
+            if peerID is not None:
+                d.manager.record(peerID, [r.Piece])
+            got.append((r, peerID))
         out.append(got)
     return out
