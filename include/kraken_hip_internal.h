@@ -258,6 +258,12 @@ int krk_piece_request_geometry(uint64_t* pieces_per_pass, uint64_t* thread_strid
  * further passes, whose state is in memory and not in registers) -- for the tests that pin
  * krk_piece_resend_round_dev's edges.  No device. */
 int krk_piece_resend_geometry(uint64_t* peers_per_pass);
+/* The shape of the SHA-256 host share as built (offload.cpp): the bytes of one device-to-host copy
+ * (a chain longer than that comes down in several), the pinned buffers an offload thread's copy
+ * ring has (a chain of more chunks than that wraps it) and those of a resumer
+ * (krk_sha256_resume_dev_on_host) -- for the tests that pin the host share and the tail handoff at
+ * their chunk and ring edges.  No device. */
+int krk_sha_offload_geometry(uint64_t* d2h_chunk_bytes, uint32_t* worker_depth, uint32_t* resumer_depth);
 
 /* ------------------------------------------------------- SHA-256 plans
  * Lanes per stream (1, 2 or 8) the library uses for a batch of n_streams streams on

@@ -263,6 +263,7 @@ def _load() -> C.CDLL:
         "krk_event_destroy": (i, [vp]),
         "krk_set_sha_host_offload": (i, [i]),
         "krk_sha_host_offload": (i, [C.POINTER(C.c_int)]),
+        "krk_sha_offload_geometry": (i, [u64p, u32p, u32p]),
         "krk_planner_calibrate": (i, []),
         "krk_sha_offload_plan": (i, [C.POINTER(C.c_uint64), C.c_uint64, i, i, C.POINTER(C.c_uint32),
                                      C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),

@@ -468,6 +468,14 @@ int krk_sha_host_offload(int* threads) {
     return KRK_OK;
 }
 
+int krk_sha_offload_geometry(uint64_t* d2h_chunk_bytes, uint32_t* worker_depth, uint32_t* resumer_depth) {
+    KRK_CHECK(d2h_chunk_bytes && worker_depth && resumer_depth, KRK_EINVAL, "sha_offload_geometry: null argument");
+    *d2h_chunk_bytes = kD2hChunk;
+    *worker_depth = Worker::depth;
+    *resumer_depth = Resumer::depth;
+    return KRK_OK;
+}
+
 static int resume_args(const uint32_t* state8, uint64_t absorbed, const uint8_t* data, uint64_t n, int final,
                        const uint8_t* digest32) {
     KRK_CHECK(state8, KRK_EINVAL, "sha256_resume: state is NULL");
