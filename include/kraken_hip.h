@@ -357,6 +357,98 @@ int krk_piece_resend_round_dev(const krk_request_torrent* torrents_host, const k
                                const krk_failed_request* failed_host, uint32_t* target_out,
                                int32_t* quota_left_out, uint32_t* n_resent_out, void* stream);
 
+/* ------------------------------------------- announce rounds
+ * Whom an announcing peer talks to: the tracker's announce (tracker/trackerserver/announce.go:75-115)
+ * for a batch of announces at one clock instant -- peerstore UpdatePeer and GetPeers
+ * (tracker/peerstore/redis.go:126-196), the blob's origins appended, PriorityPolicy.SortPeers
+ * (tracker/peerhandoutpolicy/peerhandoutpolicy.go:65-99) -- as bit-matrix work.  A torrent's peer
+ * store is a bit matrix over its P known peers (P < 2^30; the identities stay with the caller, who
+ * maps them to indices): a ring of W windows, each two rows of WP = krk_bitfield_words(P) words,
+ * member_w then complete_w.  Window w (0 = the current one) is ring row (cur_row + w) % W, at words
+ * bits_off + 2 * row * WP.  With splitmix64 as KRK_PR_SAMPLE defines it above:
+ *   wkey(w)    = splitmix64(seed ^ ((uint64)(w + 1) << 32 | 0xFFFFFFFF)) >> 32    window order
+ *   pkey(w, i) = splitmix64(seed ^ ((uint64)(w + 1) << 32 | i)) >> 32             SRANDMEMBER in window w
+ *   okey(c)    = splitmix64(seed ^ c) >> 32     final order; c = i for peer i, KRK_AN_ORIGIN | o for origin o
+ * A round of A announces has two phases:
+ *   update (UpdatePeer)    for every announce: set bit `peer` of member_0, and of complete_0 under
+ *                          KRK_AN_COMPLETE.  `bits` is read and written.
+ *   handout (getPeerHandout, GetPeers, SortPeers)   each announce on its own, over the updated rows:
+ *     under KRK_AN_COMPLETE: n_out = 0 and the label counts 0 (announce.go:96-100); otherwise
+ *     selected = {};  for the windows in ascending (wkey(w), w), while |selected| < limit:
+ *       need   = limit - |selected|
+ *       sample = the min(need, |member_w|) members of window w with the smallest (pkey(w, i), i)
+ *       selected |= sample;  complete |= sample & complete_w
+ *     (a sample may repeat peers already selected, so |selected| may grow by fewer than `need`:
+ *     redis.go:172-188 does the same);
+ *     append the torrent's O origins; drop `source`;
+ *     priority under KRK_AN_COMPLETENESS: complete peer (seeder) 0, origin 1, incomplete peer 2;
+ *              under KRK_AN_DEFAULT: 0 for all;
+ *     order by ascending (priority, okey(c), c).
+ * Tail bits past P of any row are ignored: never sampled, and the update never sets one.
+ *
+ * Three deliberate differences from the reference.  Its random choices -- ShuffleInt64s over the
+ * windows, SRANDMEMBER, the Go map order of `selected` and sort.Slice, which is not stable -- are
+ * the seeded keys above: reproducible, and the same on host and device.  All updates of a round
+ * land before any handout of the round, where the server interleaves them announce by announce.
+ * And the reference drops the source by POINTER comparison (peerhandoutpolicy.go:69), which never
+ * matches the PeerInfos the store has just built, so its server hands an announcer its own entry
+ * back; here `source` is an index, which is the intent, and KRK_AN_NONE reproduces the server.
+ *
+ * Every output element is stored by the call, the caller pre-zeroes nothing: n_out[a];
+ * handout_out[a * (limit + KRK_AN_MAX_ORIGINS) + j] = c, with KRK_AN_COMPLETE_BIT set for a complete
+ * peer (never for an origin: origins are always complete), KRK_AN_NONE for j >= n_out[a];
+ * label_counts_out[a * 3 + priority], the policy's three gauges (peer_seeder, origin,
+ * peer_incomplete; under KRK_AN_DEFAULT everything lands in slot 0).  KRK_EINVAL, refused before
+ * any output or bit is touched: P >= 2^30, W outside [1, KRK_AN_MAX_WINDOWS], O above
+ * KRK_AN_MAX_ORIGINS, a limit outside [1, KRK_AN_MAX_LIMIT], cur_row >= W, torrent >= n_torrents,
+ * peer >= P, a source that is neither < P nor KRK_AN_NONE, an unknown policy or flag bit, a
+ * non-zero `reserved`, an offset of 2^48 or more, a NULL.  A == 0 is KRK_OK.  The regions the
+ * torrents name in `bits` must not overlap. */
+#define KRK_AN_MAX_WINDOWS 8u
+#define KRK_AN_MAX_ORIGINS 8u
+#define KRK_AN_MAX_LIMIT 64u
+#define KRK_AN_DEFAULT 0u       /* peerhandoutpolicy "default" */
+#define KRK_AN_COMPLETENESS 1u  /* peerhandoutpolicy "completeness" */
+#define KRK_AN_COMPLETE 1u      /* krk_announce.flags: the peer announces as complete */
+#define KRK_AN_NONE 0xFFFFFFFFu
+#define KRK_AN_ORIGIN 0x80000000u
+#define KRK_AN_COMPLETE_BIT 0x40000000u
+typedef struct {
+    uint64_t n_peers;     /* P < 2^30 */
+    uint32_t n_windows;   /* W in [1, KRK_AN_MAX_WINDOWS] */
+    uint32_t cur_row;     /* window w (0 = current) is ring row (cur_row + w) % W */
+    uint32_t n_origins;   /* O in [0, KRK_AN_MAX_ORIGINS] */
+    uint32_t reserved;    /* 0 */
+    uint64_t bits_off;    /* first word of its 2*W rows in `bits`: (member, complete) a ring row */
+} krk_announce_torrent;
+typedef struct {
+    uint32_t torrent;     /* index into torrents[] */
+    uint32_t peer;        /* the announcer's index, < P */
+    uint32_t flags;       /* KRK_AN_COMPLETE */
+    uint32_t source;      /* index to leave out of the handout, or KRK_AN_NONE */
+    uint64_t seed;
+} krk_announce;
+/* One announce's handout phase over the rows as they are (no update).  handout_out holds
+ * limit + KRK_AN_MAX_ORIGINS entries, label_counts_out three.  No device. */
+int krk_announce_handout(const krk_announce_torrent* torrents, uint64_t n_torrents, const uint64_t* bits,
+                         const krk_announce* announce, uint32_t limit, uint32_t policy, uint32_t* handout_out,
+                         uint32_t* n_out, uint32_t* label_counts_out);
+/* The whole round on the host: every update, then every handout.  No device. */
+int krk_announce_round(const krk_announce_torrent* torrents, uint64_t n_torrents, uint64_t* bits,
+                       const krk_announce* announces, uint64_t n_announces, uint32_t limit, uint32_t policy,
+                       uint32_t* handout_out, uint32_t* n_out, uint32_t* label_counts_out);
+/* The same on the device (announce_round.hip), bit for bit, the updated rows included;
+ * asynchronous on `stream`: one launch for the updates (one thread an announce) and one for the
+ * handouts (one wave an announce).  bits_dev and the outputs are device memory or page-locked host
+ * memory (krk_host_alloc), bits_dev 8-byte and the others 4-byte aligned: anything else is
+ * KRK_EINVAL before anything is launched.  torrents_host and announces_host are checked as above
+ * and copied into the library's staging before the call returns.  KRK_ERANGE: 2^31 announces or
+ * more.  KRK_ENODEV without a gfx950 device: there is no fall-back to the host form. */
+int krk_announce_round_dev(const krk_announce_torrent* torrents_host, uint64_t n_torrents, uint64_t* bits_dev,
+                           const krk_announce* announces_host, uint64_t n_announces, uint32_t limit,
+                           uint32_t policy, uint32_t* handout_out, uint32_t* n_out, uint32_t* label_counts_out,
+                           void* stream);
+
 /* ------------------------------------------- re-piece stored MetaInfo, no blob read
  * The piece sums of a stored MetaInfo at a COARSER piece length, from the stored sums alone:
  * what a changed piece-length table (lib/metainfogen/config.go:48-80) asks of every

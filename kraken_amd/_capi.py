@@ -20,6 +20,9 @@ KRK_PLACE_AUTO, KRK_PLACE_HOST, KRK_PLACE_GPU = 0, 1, 2
 KRK_OFFLOAD_AUTO = -1
 KRK_PR_MAX_LIMIT, KRK_PR_RAREST_FIRST, KRK_PR_SAMPLE, KRK_PR_ALLOW_DUPLICATES, KRK_PR_NONE = 16, 0, 1, 0x100, 0xFFFFFFFF
 KRK_PR_EXPIRED, KRK_PR_UNSENT, KRK_PR_INVALID = 1, 2, 3
+KRK_AN_MAX_WINDOWS, KRK_AN_MAX_ORIGINS, KRK_AN_MAX_LIMIT = 8, 8, 64
+KRK_AN_DEFAULT, KRK_AN_COMPLETENESS, KRK_AN_COMPLETE = 0, 1, 1
+KRK_AN_NONE, KRK_AN_ORIGIN, KRK_AN_COMPLETE_BIT = 0xFFFFFFFF, 0x80000000, 0x40000000
 
 
 class KrakenError(RuntimeError):
@@ -64,6 +67,16 @@ class krk_failed_request(C.Structure):
 
 class krk_resend_torrent(C.Structure):
     _fields_ = [("failed_off", C.c_uint64), ("n_failed", C.c_uint64)]
+
+
+class krk_announce_torrent(C.Structure):
+    _fields_ = [("n_peers", C.c_uint64), ("n_windows", C.c_uint32), ("cur_row", C.c_uint32), ("n_origins", C.c_uint32),
+                ("reserved", C.c_uint32), ("bits_off", C.c_uint64)]
+
+
+class krk_announce(C.Structure):
+    _fields_ = [("torrent", C.c_uint32), ("peer", C.c_uint32), ("flags", C.c_uint32), ("source", C.c_uint32),
+                ("seed", C.c_uint64)]
 
 
 class krk_chunk(C.Structure):
@@ -142,6 +155,12 @@ def _load() -> C.CDLL:
         "krk_piece_resend_round_dev": (i, [C.POINTER(krk_request_torrent), C.POINTER(krk_resend_torrent), C.c_uint64, vp,
                                            vp, C.POINTER(krk_failed_request), vp, vp, vp, vp]),
         "krk_piece_resend_geometry": (i, [u64p]),
+        "krk_announce_handout": (i, [C.POINTER(krk_announce_torrent), C.c_uint64, u64p, C.POINTER(krk_announce), C.c_uint32,
+                                     C.c_uint32, u32p, u32p, u32p]),
+        "krk_announce_round": (i, [C.POINTER(krk_announce_torrent), C.c_uint64, u64p, C.POINTER(krk_announce), C.c_uint64,
+                                   C.c_uint32, C.c_uint32, u32p, u32p, u32p]),
+        "krk_announce_round_dev": (i, [C.POINTER(krk_announce_torrent), C.c_uint64, vp, C.POINTER(krk_announce), C.c_uint64,
+                                       C.c_uint32, C.c_uint32, vp, vp, vp, vp]),
         "krk_repiece_sums": (i, [u32p, C.c_uint64, C.c_int64, C.c_int64, C.c_int64, u32p, C.c_uint64]),
         "krk_repiece_batch": (i, [C.POINTER(krk_repiece_blob), C.c_uint64, u32p, u32p]),
         "krk_repiece_batch_dev": (i, [C.POINTER(krk_repiece_blob), C.c_uint64, vp, vp, vp]),

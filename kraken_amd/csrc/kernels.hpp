@@ -413,6 +413,19 @@ hipError_t launch_piece_resend(const RsTorrent* tors, uint64_t n_tors, const uin
                                const rs::Failed* failed, int32_t* left, uint32_t* mark, uint32_t* target,
                                uint32_t* n_resent, hipStream_t s);
 
+// ---------------------------------------------------------------- announce rounds
+// One announce round (announce_round.hip, announce_math.hpp): the update launch sets every
+// announcer's bits in window 0 of its torrent (atomic or), the handout launch -- one wave an
+// announce -- stores every handout[a * (limit + 8) + j], n_out[a] and labels[3 a + k].  The
+// torrents and announces are valid (an::torrent_error, an::announce_error), limit in [1, 64].
+namespace an {
+struct Torrent;
+struct Announce;
+}
+hipError_t launch_announce_round(const an::Torrent* tors, const an::Announce* anns, uint64_t n_anns, uint64_t* bits,
+                                 uint32_t limit, uint32_t policy, uint32_t* handout, uint32_t* n_out, uint32_t* labels,
+                                 hipStream_t s);
+
 // ---------------------------------------------------------------- synthetic data
 // One synthetic chunk: bytes [offset, offset + n) of the blob whose stream seed is `seed`.
 struct SynthChunk {

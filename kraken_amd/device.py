@@ -8,7 +8,7 @@ import os
 import numpy as np
 
 from ._capi import (check, krk_blob, krk_file_blob, krk_chunk, krk_launch_rec, krk_nodes, krk_planner_rates,
-                    krk_request_torrent, krk_resend_torrent, krk_failed_request, lib)
+                    krk_request_torrent, krk_resend_torrent, krk_failed_request, krk_announce_torrent, krk_announce, lib)
 
 ALIGN = 256  # every blob starts 256-byte aligned in the arena
 
@@ -1025,6 +1025,111 @@ def piece_resend_geometry() -> int:
     s = C.c_uint64()
     check(lib.krk_piece_resend_geometry(C.byref(s)))
     return int(s.value)
+
+
+AN_MAX_WINDOWS, AN_MAX_ORIGINS, AN_MAX_LIMIT = 8, 8, 64
+AN_DEFAULT, AN_COMPLETENESS, AN_COMPLETE = 0, 1, 1
+AN_NONE, AN_ORIGIN, AN_COMPLETE_BIT = 0xFFFFFFFF, 0x80000000, 0x40000000
+
+
+class AnnounceBatch:
+    """The torrents and announces of an announce round.  torrents: (n_peers, n_windows, cur_row,
+    n_origins) each; their peer stores -- 2 * n_windows rows of krk_bitfield_words(n_peers) words,
+    (member, complete) a ring row -- are packed back to back, torrent t's from word .bits_off[t].
+    announces: (torrent, peer, flags, source, seed) each.  .structs / .announces are the
+    krk_announce_torrent / krk_announce arrays."""
+
+    def __init__(self, torrents, announces):
+        torrents, announces = [tuple(int(x) for x in t) for t in torrents], [tuple(int(x) for x in a) for a in announces]
+        k = len(torrents)
+        words = [2 * w * ((p + 63) // 64) for p, w, _, _ in torrents]
+        self.bits_off = np.zeros(k + 1, dtype=np.uint64)
+        self.bits_off[1:] = np.cumsum(words)
+        self.total_words = int(self.bits_off[-1])
+        self.structs = (krk_announce_torrent * max(k, 1))()
+        for t, (p, w, cur, o) in enumerate(torrents):
+            self.structs[t] = krk_announce_torrent(p, w, cur, o, 0, int(self.bits_off[t]))
+        self.n_torrents, self.n_announces = k, len(announces)
+        self.announces = (krk_announce * max(len(announces), 1))()
+        for j, a in enumerate(announces):
+            self.announces[j] = krk_announce(*a)
+
+    def __len__(self):
+        return self.n_torrents
+
+
+class AnnounceOutputs:
+    """The outputs of announce_round_dev, in device memory or (pinned=True) in page-locked host
+    memory the kernel writes over PCIe: .handout (uint32, limit + AN_MAX_ORIGINS an announce),
+    .n_out (uint32 an announce), .labels (uint32, three an announce)."""
+
+    def __init__(self, batch: AnnounceBatch, limit: int, pinned: bool = False):
+        self.n, self.cap, self.pinned = batch.n_announces, int(limit) + AN_MAX_ORIGINS, pinned
+        make = (lambda k: PinnedArray((max(k, 1),), np.uint32)) if pinned else (lambda k: DeviceBuffer(max(k, 1) * 4))
+        self.handout, self.n_out, self.labels = make(self.n * self.cap), make(self.n), make(self.n * 3)
+
+    def fill(self, byte: int):
+        """Every output byte set to `byte` (tests: the call must overwrite all of it)."""
+        for b in (self.handout, self.n_out, self.labels):
+            if self.pinned:
+                b.a.view(np.uint8)[:] = byte
+            else:
+                b.from_host(np.full(b.nbytes, byte, dtype=np.uint8))
+
+    def to_host(self):
+        """(handout (A, cap), n_out (A,), labels (A, 3)), once the call's stream has run."""
+        def get(b, k):
+            return b.a[:k].copy() if self.pinned else b.to_host(np.uint32, k)
+        return get(self.handout, self.n * self.cap).reshape(self.n, self.cap), get(self.n_out, self.n), \
+            get(self.labels, self.n * 3).reshape(self.n, 3)
+
+
+def _announce_bits(batch: AnnounceBatch, bits, who: str):
+    if not (isinstance(bits, np.ndarray) and bits.dtype == np.uint64 and bits.flags.c_contiguous):
+        raise ValueError(f"{who}: bits must be a contiguous uint64 array")
+    if bits.size < batch.total_words:
+        raise ValueError(f"{who}: {bits.size} words for a batch of {batch.total_words}")
+    return bits
+
+
+def announce_handout(batch: AnnounceBatch, bits, k: int, limit: int, policy: int = AN_DEFAULT):
+    """krk_announce_handout: announce k's handout over the rows as they are (no update).  Returns
+    (handout with limit + AN_MAX_ORIGINS entries, n_out, the three label counts)."""
+    b = _announce_bits(batch, bits, "announce_handout")
+    if not 0 <= k < batch.n_announces:
+        raise IndexError(f"announce_handout: announce {k} of {batch.n_announces}")
+    handout = np.zeros(max(int(limit), 0) + AN_MAX_ORIGINS, dtype=np.uint32)
+    labels, n = np.zeros(3, dtype=np.uint32), C.c_uint32()
+    check(lib.krk_announce_handout(batch.structs, len(batch), _p(b, C.c_uint64), C.byref(batch.announces[k]), limit, policy,
+                                   _p(handout, C.c_uint32), C.byref(n), _p(labels, C.c_uint32)))
+    return handout, int(n.value), labels
+
+
+def announce_round(batch: AnnounceBatch, bits, limit: int, policy: int = AN_DEFAULT):
+    """krk_announce_round: the whole announce round on the host.  bits: a contiguous uint64 array
+    in the batch's layout, UPDATED IN PLACE.  Returns (handout (A, limit + AN_MAX_ORIGINS), n_out
+    (A,), labels (A, 3))."""
+    b = _announce_bits(batch, bits, "announce_round")
+    n, cap = batch.n_announces, max(int(limit), 0) + AN_MAX_ORIGINS
+    handout, n_out, labels = np.zeros((n, cap), np.uint32), np.zeros(n, np.uint32), np.zeros((n, 3), np.uint32)
+    check(lib.krk_announce_round(batch.structs, len(batch), _p(b, C.c_uint64), batch.announces, n, limit, policy,
+                                 _p(handout, C.c_uint32), _p(n_out, C.c_uint32), _p(labels, C.c_uint32)))
+    return handout, n_out, labels
+
+
+def announce_round_dev(batch: AnnounceBatch, bits_dev, limit: int, policy: int = AN_DEFAULT,
+                       out: AnnounceOutputs | None = None, stream=None):
+    """krk_announce_round_dev: the announce round on the device.  bits_dev: DeviceBuffer or
+    PinnedArray in the batch's layout, updated in place.  out: AnnounceOutputs to fill
+    asynchronously on `stream` (returned); None: (handout, n_out, labels), returned once the stream
+    has run the call."""
+    dst = AnnounceOutputs(batch, limit, pinned=True) if out is None else out
+    check(lib.krk_announce_round_dev(batch.structs, len(batch), bits_dev.ptr, batch.announces, batch.n_announces, limit,
+                                     policy, dst.handout.ptr, dst.n_out.ptr, dst.labels.ptr, stream))
+    if out is not None:
+        return out
+    check(lib.krk_stream_sync(stream))
+    return dst.to_host()
 
 
 class KernelTimer:
