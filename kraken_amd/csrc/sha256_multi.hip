@@ -535,7 +535,8 @@ struct TwoLaneConst {
 // statement leaves it no reason to, and the disassembly shows none, but it is a property
 // of the generated code: after a compiler change, or any edit of the loop in
 // sha256_w8_kernel, check in the disassembly (tools/sha_isa.py --lanes 8 finds the loop)
-// that between the block statements only SALU bookkeeping and the address adds remain.
+// that between the block statements only SALU bookkeeping and the address adds remain
+// (whole steps), plus, in the ragged end, the v_cmp of the snapshot masks into SGPR pairs.
 constexpr int kHeld8 = 9;
 #define KRK_SHA8_RD(Q0, Q1, BASE, OFF, Q) \
     "ds_read_b128 v[" #Q0 ":" #Q1 "], %[" #BASE "] offset:%[" #OFF "]+" #Q "*1024\n\t"
@@ -568,22 +569,86 @@ constexpr int kHeld8 = 9;
 //      half's H3 (partner's hA[1], via DPP) and the feed-forward of h (hE[3]); A's
 //      rounds 62, 63 read e63, e64 through the cross add from registers E has just
 //      fed forward, so A's z gives back H5 now and H4 after n = 64;
-//      hE <- R where i < this stream's block count;
+//      hE <- R where the mask mE is set (block i is one of this stream's);
 //   n = 64: E round 0 of block i + 1 (W = its KW0 .. KW1), A round 62;
 //   F2: E's round 1 reads raw a62 as d: z += partner's hA[0] (H2); A: z -= H4
 //      (both in one register cc formed in F1);
 //   n = 65: E round 1, A round 63;
 //   F3 (A finished block i): A's round 0 of block i + 1 takes -d from z formed on raw
-//      a61: z -= hA[1]; R += hA; hA <- R where i < the block count.
+//      a61: z -= hA[1]; R += hA; hA <- R where mA is set.
 // A finished stream's lanes keep computing on garbage; their hE / hA stay frozen.
 // cur / nxt: LDS byte addresses (a VGPR and a constant each) of quad 0 of this block's
 // and the next block's column; k: the first kHeld8 W quads, this block's on entry and
 // the next block's (in flight) on return.
-template <uint32_t kCurOff, uint32_t kNxtOff>
+// mE / mA: where hE / hA take the fed-forward value (a stream's lanes of that half while the
+// block is one of the stream's), each a wave mask in an SGPR pair: the block holds no compare
+// and leaves vcc alone.  Whole steps pass the two constant half masks (sha256_w8_kernel).
+#define KRK_SHA8_SNAP(H, M)                                              \
+    "v_cndmask_b32_e64 %[" #H "0], %[" #H "0], %[R0], %[" #M "]\n\t"     \
+    "v_cndmask_b32_e64 %[" #H "1], %[" #H "1], %[R3], %[" #M "]\n\t"     \
+    "v_cndmask_b32_e64 %[" #H "2], %[" #H "2], %[R2], %[" #M "]\n\t"     \
+    "v_cndmask_b32_e64 %[" #H "3], %[" #H "3], %[R1], %[" #M "]\n\t"
+#define KRK_SHA8_F1                                                              \
+    "v_sub_u32_e32 %[cc], %[a0], %[e0]\n\t"                                      \
+    "v_sub_u32_e32 %[dd], %[a1], %[e1]\n\t"                                      \
+    "v_add_u32_e32 %[R0], %[e0], %[R0]\n\t"                                      \
+    "v_add_u32_e32 %[R3], %[e1], %[R3]\n\t"                                      \
+    "v_mov_b32_dpp %[c2], %[cc] row_ror:8 row_mask:0xf bank_mask:0xf\n\t"        \
+    "v_add_u32_dpp %[z], %[dd], %[z] row_ror:8 row_mask:0xf bank_mask:0xf\n\t"   \
+    "v_add_u32_e32 %[R2], %[e2], %[R2]\n\t"                                      \
+    "v_add_u32_e32 %[R1], %[e3], %[R1]\n\t"                                      \
+    "v_add_u32_e32 %[z], %[e3], %[z]\n\t"                                        \
+    KRK_SHA8_SNAP(e, mE)
+#define KRK_SHA8_F2 "v_add_u32_e32 %[z], %[c2], %[z]\n\t"
+#define KRK_SHA8_F3                                 \
+    "v_sub_u32_e32 %[z], %[z], %[a1]\n\t"           \
+    "v_add_u32_e32 %[R0], %[a0], %[R0]\n\t"         \
+    "v_add_u32_e32 %[R3], %[a1], %[R3]\n\t"         \
+    "v_add_u32_e32 %[R2], %[a2], %[R2]\n\t"         \
+    "v_add_u32_e32 %[R1], %[a3], %[R1]\n\t"         \
+    KRK_SHA8_SNAP(a, mA)
+// order of the text: quad-times 0 .. 14 (bursts A and B after the first round of quad-times
+// 0 and 8), n = 62, n = 63 (on the next block's KW0), F1, n = 64, F2, n = 65, F3
+#define KRK_SHA8_BLOCK(F1, F2, F3)                                \
+    KRK_SHA8_QT(v67, v68, v69, v70, KRK_SHA8_BURST_A)             \
+    KRK_SHA8_QT(v71, v72, v73, v74, "")                           \
+    KRK_SHA8_QT(v75, v76, v77, v78, "")                           \
+    KRK_SHA8_QT(v79, v80, v81, v82, "")                           \
+    KRK_SHA8_QT(v83, v84, v85, v86, "")                           \
+    KRK_SHA8_QT(v87, v88, v89, v90, "")                           \
+    KRK_SHA8_QT(v91, v92, v93, v94, "")                           \
+    KRK_SHA8_QT(v95, v96, v97, v98, "")                           \
+    KRK_SHA8_QT(v99, v100, v101, v102, KRK_SHA8_BURST_B)          \
+    KRK_SHA8_QT(v103, v104, v105, v106, "")                       \
+    KRK_SHA8_QT(v107, v108, v109, v110, "")                       \
+    KRK_SHA8_QT(v111, v112, v113, v114, "")                       \
+    KRK_SHA8_QT(v115, v116, v117, v118, "")                       \
+    KRK_SHA8_QT(v119, v120, v121, v122, "")                       \
+    KRK_SHA8_QT(v123, v124, v125, v126, "")                       \
+    KRK_SHA8_ROUND_(R2, R1, R0, R3, "v127")                       \
+    KRK_SHA8_ROUND_(R3, R2, R1, R0, "v64")                        \
+    F1 KRK_SHA8_ROUND_(R0, R3, R2, R1, "v65") F2 KRK_SHA8_ROUND_(R1, R0, R3, R2, "v66") F3
+#define KRK_SHA8_BLOCK_OPERANDS                                                                              \
+    : [t1] "=&v"(t1), [t2] "=&v"(t2), [k] "=&v"(kk), [p] "=&v"(p), [cc] "=&v"(cc), [dd] "=&v"(dd),           \
+      [c2] "=&v"(c2), [z] "+v"(z),                                                                           \
+      [R0] "+v"(R0), [R1] "+v"(R1), [R2] "+v"(R2), [R3] "+v"(R3), [e0] "+v"(hE[0]),                          \
+      [e1] "+v"(hE[1]), [e2] "+v"(hE[2]), [e3] "+v"(hE[3]), [a0] "+v"(hA[0]), [a1] "+v"(hA[1]),              \
+      [a2] "+v"(hA[2]), [a3] "+v"(hA[3]),                                                                    \
+      /* in flight on return (see INVARIANT above): valid only after the next wait A */                      \
+      "+{v[64:67]}"(k[0]), "+{v[68:71]}"(k[1]), "+{v[72:75]}"(k[2]), "+{v[76:79]}"(k[3]),                    \
+      "+{v[80:83]}"(k[4]), "+{v[84:87]}"(k[5]), "+{v[88:91]}"(k[6]), "+{v[92:95]}"(k[7]),                    \
+      "+{v[96:99]}"(k[8])                                                                                    \
+    : KRK_SHA8_CONSTS, [mE] "s"(mE), [mA] "s"(mA), [cb] "v"(cur),                                            \
+      [nb] "v"(nxt), [co] "n"(kCurOff), [no] "n"(kNxtOff)                                                    \
+    : "memory", "v100", "v101", "v102", "v103", "v104", "v105", "v106", "v107", "v108",                      \
+      "v109", "v110", "v111", "v112", "v113", "v114", "v115", "v116", "v117", "v118", "v119", "v120",        \
+      "v121", "v122", "v123", "v124", "v125", "v126", "v127"
+// kBoundary false (diagnostic build only, WRONG digests): the block without F1 .. F3, to
+// price them (plan 109, profiles/r08/sha8_boundary_cost.jsonl).
+template <uint32_t kCurOff, uint32_t kNxtOff, bool kBoundary>
 __device__ __forceinline__ void block8p(uint32_t& R0, uint32_t& R1, uint32_t& R2, uint32_t& R3, uint32_t& z,
-                                        uint32_t hE[4], uint32_t hA[4], uint32_t mineE, uint32_t mineA,
-                                        uint32_t i, uint32_t cur, uint32_t nxt, const TwoLaneConst& c,
-                                        u32x4 k[kHeld8]) {
+                                        uint32_t hE[4], uint32_t hA[4], uint64_t mE, uint64_t mA, uint32_t cur,
+                                        uint32_t nxt, const TwoLaneConst& c, u32x4 k[kHeld8]) {
     // The cross terms of F1 .. F3 go through one DPP each: every lane forms hA - hE of
     // its own (E lanes: -hE, A lanes: hA) and reads its partner's, so E picks up the A
     // half's H2 / H3 and A gives back E's H4 / H5.  (v_subrev_u32_dpp swizzles its second
@@ -591,67 +656,18 @@ __device__ __forceinline__ void block8p(uint32_t& R0, uint32_t& R1, uint32_t& R2
     // instruction reads is written at least two instructions earlier; a read or a wait
     // between two rounds only lengthens those distances.
     uint32_t t1, t2, kk, p, cc, dd, c2;
-    // order of the text: quad-times 0 .. 14 (bursts A and B after the first round of quad-times
-    // 0 and 8), n = 62, n = 63 (on the next block's KW0), F1, n = 64, F2, n = 65, F3
-    asm volatile(KRK_SHA8_QT(v67, v68, v69, v70, KRK_SHA8_BURST_A)
-                 KRK_SHA8_QT(v71, v72, v73, v74, "")
-                 KRK_SHA8_QT(v75, v76, v77, v78, "")
-                 KRK_SHA8_QT(v79, v80, v81, v82, "")
-                 KRK_SHA8_QT(v83, v84, v85, v86, "")
-                 KRK_SHA8_QT(v87, v88, v89, v90, "")
-                 KRK_SHA8_QT(v91, v92, v93, v94, "")
-                 KRK_SHA8_QT(v95, v96, v97, v98, "")
-                 KRK_SHA8_QT(v99, v100, v101, v102, KRK_SHA8_BURST_B)
-                 KRK_SHA8_QT(v103, v104, v105, v106, "")
-                 KRK_SHA8_QT(v107, v108, v109, v110, "")
-                 KRK_SHA8_QT(v111, v112, v113, v114, "")
-                 KRK_SHA8_QT(v115, v116, v117, v118, "")
-                 KRK_SHA8_QT(v119, v120, v121, v122, "")
-                 KRK_SHA8_QT(v123, v124, v125, v126, "")
-                 KRK_SHA8_ROUND_(R2, R1, R0, R3, "v127")
-                 KRK_SHA8_ROUND_(R3, R2, R1, R0, "v64")
-                 "v_sub_u32_e32 %[cc], %[a0], %[e0]\n\t"
-                 "v_sub_u32_e32 %[dd], %[a1], %[e1]\n\t"
-                 "v_add_u32_e32 %[R0], %[e0], %[R0]\n\t"
-                 "v_add_u32_e32 %[R3], %[e1], %[R3]\n\t"
-                 "v_mov_b32_dpp %[c2], %[cc] row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_add_u32_dpp %[z], %[dd], %[z] row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_add_u32_e32 %[R2], %[e2], %[R2]\n\t"
-                 "v_add_u32_e32 %[R1], %[e3], %[R1]\n\t"
-                 "v_add_u32_e32 %[z], %[e3], %[z]\n\t"
-                 "v_cmp_lt_u32_e32 vcc, %[i], %[mineE]\n\t"
-                 "v_cndmask_b32_e32 %[e0], %[e0], %[R0], vcc\n\t"
-                 "v_cndmask_b32_e32 %[e1], %[e1], %[R3], vcc\n\t"
-                 "v_cndmask_b32_e32 %[e2], %[e2], %[R2], vcc\n\t"
-                 "v_cndmask_b32_e32 %[e3], %[e3], %[R1], vcc\n\t"
-                 KRK_SHA8_ROUND_(R0, R3, R2, R1, "v65")
-                 "v_add_u32_e32 %[z], %[c2], %[z]\n\t"
-                 KRK_SHA8_ROUND_(R1, R0, R3, R2, "v66")
-                 "v_sub_u32_e32 %[z], %[z], %[a1]\n\t"
-                 "v_add_u32_e32 %[R0], %[a0], %[R0]\n\t"
-                 "v_add_u32_e32 %[R3], %[a1], %[R3]\n\t"
-                 "v_add_u32_e32 %[R2], %[a2], %[R2]\n\t"
-                 "v_add_u32_e32 %[R1], %[a3], %[R1]\n\t"
-                 "v_cmp_lt_u32_e32 vcc, %[i], %[mineA]\n\t"
-                 "v_cndmask_b32_e32 %[a0], %[a0], %[R0], vcc\n\t"
-                 "v_cndmask_b32_e32 %[a1], %[a1], %[R3], vcc\n\t"
-                 "v_cndmask_b32_e32 %[a2], %[a2], %[R2], vcc\n\t"
-                 "v_cndmask_b32_e32 %[a3], %[a3], %[R1], vcc\n\t"
-                 : [t1] "=&v"(t1), [t2] "=&v"(t2), [k] "=&v"(kk), [p] "=&v"(p), [cc] "=&v"(cc), [dd] "=&v"(dd),
-                   [c2] "=&v"(c2), [z] "+v"(z),
-                   [R0] "+v"(R0), [R1] "+v"(R1), [R2] "+v"(R2), [R3] "+v"(R3), [e0] "+v"(hE[0]),
-                   [e1] "+v"(hE[1]), [e2] "+v"(hE[2]), [e3] "+v"(hE[3]), [a0] "+v"(hA[0]), [a1] "+v"(hA[1]),
-                   [a2] "+v"(hA[2]), [a3] "+v"(hA[3]),
-                   // in flight on return (see INVARIANT above): valid only after the next wait A
-                   "+{v[64:67]}"(k[0]), "+{v[68:71]}"(k[1]), "+{v[72:75]}"(k[2]), "+{v[76:79]}"(k[3]),
-                   "+{v[80:83]}"(k[4]), "+{v[84:87]}"(k[5]), "+{v[88:91]}"(k[6]), "+{v[92:95]}"(k[7]),
-                   "+{v[96:99]}"(k[8])
-                 : KRK_SHA8_CONSTS, [i] "s"(i), [mineE] "v"(mineE), [mineA] "v"(mineA), [cb] "v"(cur),
-                   [nb] "v"(nxt), [co] "n"(kCurOff), [no] "n"(kNxtOff)
-                 : "vcc", "memory", "v100", "v101", "v102", "v103", "v104", "v105", "v106", "v107", "v108",
-                   "v109", "v110", "v111", "v112", "v113", "v114", "v115", "v116", "v117", "v118", "v119", "v120",
-                   "v121", "v122", "v123", "v124", "v125", "v126", "v127");
+    if constexpr (kBoundary) {
+        asm volatile(KRK_SHA8_BLOCK(KRK_SHA8_F1, KRK_SHA8_F2, KRK_SHA8_F3) KRK_SHA8_BLOCK_OPERANDS);
+    } else {
+        asm volatile(KRK_SHA8_BLOCK("", "", "") KRK_SHA8_BLOCK_OPERANDS);
+    }
 }
+#undef KRK_SHA8_BLOCK_OPERANDS
+#undef KRK_SHA8_BLOCK
+#undef KRK_SHA8_F3
+#undef KRK_SHA8_F2
+#undef KRK_SHA8_F1
+#undef KRK_SHA8_SNAP
 #undef KRK_SHA8_QT
 #undef KRK_SHA8_BURST_A
 #undef KRK_SHA8_BURST_B
@@ -1045,7 +1061,8 @@ sha256_ws_kernel(const ShaJob* __restrict__ jobs, uint32_t n_jobs, uint8_t* __re
 // an LDS broadcast), its A quad the all-1 slot.
 // kTiming 1 (diagnostic build only, WRONG digests): the producer returns at once and
 // the consumer runs its rounds on whatever the ring holds with no barriers -- the
-// consumer's own time per block.
+// consumer's own time per block.  kTiming 4: the same without the block-boundary ops
+// F1 .. F3 of block8p, which prices them.
 template <int kTiming, int kGroups>
 __global__ void __launch_bounds__(128 * kGroups)
 sha256_w8_kernel(const ShaJob* __restrict__ jobs, uint32_t n_jobs, uint8_t* __restrict__ out_digest,
@@ -1069,7 +1086,8 @@ sha256_w8_kernel(const ShaJob* __restrict__ jobs, uint32_t n_jobs, uint8_t* __re
     const uint32_t mine = live ? job_blocks(job) : 0u;
     const uint32_t nb = workgroup_blocks<kGroups>(jobs, n_jobs, sbase, kPer, me, grp, mine);
 
-    if (producer && kTiming == 1) return;
+    constexpr bool kAlone = kTiming == 1 || kTiming == 4;  // consumer only (4: without F1 .. F3)
+    if (producer && kAlone) return;
     if (producer) {
 #pragma unroll
         for (int q = 0; q < 16; ++q) *reinterpret_cast<u32x4*>(ring + kw_index(kRing8, q, lane)) = u32x4{1u, 1u, 1u, 1u};
@@ -1128,24 +1146,60 @@ sha256_w8_kernel(const ShaJob* __restrict__ jobs, uint32_t n_jobs, uint8_t* __re
     }
     const uint32_t mineE = is_e ? mine : 0u, mineA = is_e ? 0u : mine;
     uint32_t R0 = h[0], R3 = h[1], R2 = h[2], R1 = h[3], z = 0;
-    // Four blocks an iteration (a step's 8 blocks never straddle an iteration): one block
-    // an iteration ran at 52.9 MB/s a stream, two at 55.0 (fewer taken branches and
-    // less loop bookkeeping per block); with W read in groups of three quads (the form
-    // before the bursts of block8p), four 59.1 vs two 58.8,
-    // eight 59.1 (profiles/r02/sha8_unroll.jsonl).
-    constexpr uint32_t kU = 4;
+    constexpr uint32_t kU = 4;  // blocks an iteration of the ragged end
     static_assert(kStep8 % kU == 0, "blocks per iteration divide a step");
     if (nb) {  // step 0's barrier, the first quads, and (pipelined) rounds 0, 1 of block 0
-        if (kTiming == 0) __builtin_amdgcn_s_barrier();
+        if (!kAlone) __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
 #pragma unroll
         for (int q = 0; q < kHeld8; ++q) kq[q] = *reinterpret_cast<const u32x4*>(ring + lbase + 256 * q);
         prologue8p(R0, R1, R2, R3, z, h, is_e, c, kq[0]);
     }
-    for (uint32_t i = 0; i < nb; i += kU) {
+    constexpr uint32_t kB = 4u * binc;  // bytes from a block's column to the next block's
+    constexpr bool kBnd = kTiming != 4;
+    uint32_t i = 0;
+    // Whole steps, 8 blocks an iteration, while every live stream of the wave has the whole
+    // step: one barrier, one slot change (a scalar offset that wraps after kRing8 steps), no
+    // guard between the blocks, and the chaining snapshot under the two constant half masks,
+    // so no compare either.  Same-box C2 launches, three of each build a process, three
+    // processes interleaved (profiles/r08/sha8_boundary_ab.jsonl): the four-block guarded loop
+    // below alone 1,741 ms, whole steps with the compares kept 1,725, with the masks 1,714.
+    {
+        constexpr uint32_t kSlotBytes = 4u * uint32_t(kSlotWords);
+        constexpr uint64_t kMaskE = 0x00ff00ff00ff00ffull, kMaskA = ~kMaskE;  // quads 0, 1 of a row / quads 2, 3
+        const uint32_t emask = is_e ? ~0u : 0u;
+        const uint32_t nfull = min(nb, wave_min(live ? mine : ~0u)) & ~uint32_t(kStep8 - 1);
+        uint32_t soff = 0;  // byte offset of the step's ring slot (E lanes; the A lanes stay in the all-1 slot)
+        for (; i < nfull; i += kStep8) {
+            if (i) {
+                if (!kAlone) __builtin_amdgcn_s_barrier();
+                asm volatile("" ::: "memory");
+            }
+            const uint32_t noff = soff == (kRing8 - 1) * kSlotBytes ? 0u : soff + kSlotBytes;
+            // block u of the step sits u * kB bytes past cur, a constant offset of its reads;
+            // only the step's last block has its successor in the next slot
+            const uint32_t cur = lbyte + (soff & emask), nxt = lbyte + (noff & emask);
+            block8p<0, kB, kBnd>(R0, R1, R2, R3, z, hE, hA, kMaskE, kMaskA, cur, cur, c, kq);
+            block8p<kB, 2 * kB, kBnd>(R0, R1, R2, R3, z, hE, hA, kMaskE, kMaskA, cur, cur, c, kq);
+            block8p<2 * kB, 3 * kB, kBnd>(R0, R1, R2, R3, z, hE, hA, kMaskE, kMaskA, cur, cur, c, kq);
+            block8p<3 * kB, 4 * kB, kBnd>(R0, R1, R2, R3, z, hE, hA, kMaskE, kMaskA, cur, cur, c, kq);
+            block8p<4 * kB, 5 * kB, kBnd>(R0, R1, R2, R3, z, hE, hA, kMaskE, kMaskA, cur, cur, c, kq);
+            block8p<5 * kB, 6 * kB, kBnd>(R0, R1, R2, R3, z, hE, hA, kMaskE, kMaskA, cur, cur, c, kq);
+            block8p<6 * kB, 7 * kB, kBnd>(R0, R1, R2, R3, z, hE, hA, kMaskE, kMaskA, cur, cur, c, kq);
+            block8p<7 * kB, 0, kBnd>(R0, R1, R2, R3, z, hE, hA, kMaskE, kMaskA, cur, nxt, c, kq);
+            soff = noff;
+        }
+        slot = soff / kSlotBytes;
+        voff = vslot = (soff / 4u) & emask;
+    }
+    // The ragged end -- from the step in which the wave's shortest live stream ends -- and
+    // the last 1 .. 7 blocks: four blocks an iteration (a step's 8 blocks never straddle an
+    // iteration), each behind its guard, the snapshot masks compared per block (a v_cmp into
+    // an SGPR pair between the block statements, which touches no W register).
+    for (; i < nb; i += kU) {
         const uint32_t jj = i & (kStep8 - 1);
         if (jj == 0 && i) {
-            if (kTiming == 0) __builtin_amdgcn_s_barrier();
+            if (!kAlone) __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
         }
         const bool last = jj == kStep8 - kU;
@@ -1155,16 +1209,18 @@ sha256_w8_kernel(const ShaJob* __restrict__ jobs, uint32_t n_jobs, uint8_t* __re
         const uint32_t cur = lbyte + 4u * voff;
         voff = last ? nvslot : voff + kU * binc;
         const uint32_t nxt = lbyte + 4u * voff;
-        constexpr uint32_t kB = 4u * binc;  // bytes from a block's column to the next block's
+        // wave masks of i + U < mineE / mineA (36: unsigned less than)
+#define KRK_M8(U) __builtin_amdgcn_uicmp(i + U, mineE, 36), __builtin_amdgcn_uicmp(i + U, mineA, 36)
         // Inside a lambda on purpose: called straight from the loop body the same four
         // statements get other VGPR numbers; through the by-reference captures the code
-        // is byte for byte the one that was measured.
+        // is the one that was measured.
         [&] {  // block 0 is past nb only in the wave's last iteration
-            block8p<0, kB>(R0, R1, R2, R3, z, hE, hA, mineE, mineA, i, cur, cur, c, kq);
-            if (i + 1 < nb) block8p<kB, 2 * kB>(R0, R1, R2, R3, z, hE, hA, mineE, mineA, i + 1, cur, cur, c, kq);
-            if (i + 2 < nb) block8p<2 * kB, 3 * kB>(R0, R1, R2, R3, z, hE, hA, mineE, mineA, i + 2, cur, cur, c, kq);
-            if (i + 3 < nb) block8p<3 * kB, 0>(R0, R1, R2, R3, z, hE, hA, mineE, mineA, i + 3, cur, nxt, c, kq);
+            block8p<0, kB, kBnd>(R0, R1, R2, R3, z, hE, hA, KRK_M8(0), cur, cur, c, kq);
+            if (i + 1 < nb) block8p<kB, 2 * kB, kBnd>(R0, R1, R2, R3, z, hE, hA, KRK_M8(1), cur, cur, c, kq);
+            if (i + 2 < nb) block8p<2 * kB, 3 * kB, kBnd>(R0, R1, R2, R3, z, hE, hA, KRK_M8(2), cur, cur, c, kq);
+            if (i + 3 < nb) block8p<3 * kB, 0, kBnd>(R0, R1, R2, R3, z, hE, hA, KRK_M8(3), cur, nxt, c, kq);
         }();
+#undef KRK_M8
         if (last) {
             slot = slot == kRing8 - 1 ? 0u : slot + 1;
             vslot = nvslot;
@@ -1249,7 +1305,7 @@ static hipError_t launch_multi(const ShaJob* jobs, uint32_t n_jobs, uint8_t* out
 // kernel.  Every production plan is bit-exact; KRK_SHA_PLAN_AUTO is no row, auto_plan()
 // below picks one.  The timing diagnostics (kTiming != 0: WRONG digests, see
 // sha256_ws_kernel and sha256_w8_kernel) and the one-lane-does-everything kernel exist
-// only in the diagnostic build (make diag, -DKRK_DIAG), as plans 100 .. 108.
+// only in the diagnostic build (make diag, -DKRK_DIAG), as plans 100 .. 109.
 struct ShaPlan {
     int id, lanes, pairs, timing;
     ShaLaunch launch;
@@ -1275,6 +1331,7 @@ constexpr ShaPlan kShaPlans[] = {
     sha_plan_row<2, 1, 2>(106),  // producer only
     sha_plan_row<2, 1, 3>(107),  // producer only, no global loads
     sha_plan_row<8, 1, 1>(108),  // rounds-only consumer
+    sha_plan_row<8, 1, 4>(109),  // rounds-only consumer without the block-boundary ops F1 .. F3
 #endif
 };
 
