@@ -449,6 +449,146 @@ int krk_announce_round_dev(const krk_announce_torrent* torrents_host, uint64_t n
                            uint32_t policy, uint32_t* handout_out, uint32_t* n_out, uint32_t* label_counts_out,
                            void* stream);
 
+/* ------------------------------------------- connection rounds
+ * The step between an announce's handout and a request round's "P connected peers":
+ * connstate.State (lib/torrent/scheduler/connstate/state.go) and the scheduler events that drive
+ * it (lib/torrent/scheduler/events.go:125-285, :369-392) for every torrent of a batch.  The caller
+ * maps a torrent's known peers to indices (the index space of its request rounds), P < 2^30,
+ * WP = krk_bitfield_words(P).  A torrent's state:
+ *   bits[bits_off ..]          two rows of WP words: active, then pending
+ *   expiry[peer_off + p]       the blacklist entry's expiration in the caller's clock units, 0: never
+ *   capacity[t]                MaxOpenConnectionsPerTorrent minus the pending and active conns
+ *                              (state.go:160-164); the caller initialises it
+ * Tail bits past P of any row, neighbour rows included, are ignored and never set.
+ *
+ * One round, scalars now, blacklist_duration, max_mutual and flags (KRK_CN_DISABLE_BLACKLIST),
+ * runs a torrent's three lists in a fixed order.  Blacklisted(p) is expiry_p > now (state.go:46-52).
+ * blacklist(p): nothing under KRK_CN_DISABLE_BLACKLIST; else if Blacklisted(p) the status gains
+ * KRK_CN_STILL_BLACKLISTED (state.go:128-130) and the entry stays; else
+ * expiry_p = now + blacklist_duration and the status gains KRK_CN_BLACKLISTED_NOW.
+ *  1. transitions {peer, kind}, strictly ascending by peer (one a connection a round; they commute):
+ *       ESTABLISHED (MovePendingToActive)  pending: cleared, active set, OK; else NOT_PENDING.
+ *                                          A closed conn is the caller's to filter.
+ *       FAILED_IN   (failedIncomingHandshakeEvent)  pending: cleared, capacity + 1, OK | FREED; else NOOP
+ *       FAILED_OUT  (failedOutgoingHandshakeEvent)  as FAILED_IN, then blacklist(p) in both cases
+ *       CLOSED      (connClosedEvent)      active: cleared, capacity + 1, OK | FREED; else NOOP;
+ *                                          then blacklist(p) in both cases, as the reference does
+ *  2. incoming handshakes {peer, neigh_off}, in list order; neigh_off is a word offset into
+ *     `neighbors` of one WP-word row (the remote's RemoteBitfields() keys as bits), or
+ *     KRK_CN_NO_ROW.  AddPending's checks in its order (state.go:158-184):
+ *       capacity == 0 -> AT_CAPACITY; pending_p -> ALREADY_PENDING; active_p -> ALREADY_ACTIVE;
+ *       popcount(neigh & (active | pending)) > max_mutual -> TOO_MANY_MUTUAL (strictly greater);
+ *       else pending_p = 1, capacity - 1 -> OK.
+ *     An admission is seen by the entries after it.  The blacklist is not consulted, as in the reference.
+ *  3. dials: candidate peer indices, one announce handout in handout order
+ *     (announceResultEvent.apply, events.go:257-285).  Under KRK_CN_TORRENT_COMPLETE every entry is
+ *     TORRENT_IS_COMPLETE and nothing changes.  Otherwise, in list order:
+ *       p == self_peer -> SELF; Blacklisted(p) -> BLACKLISTED (also under DISABLE_BLACKLIST, as the
+ *       reference); capacity == 0 -> AT_CAPACITY; pending_p -> ALREADY_PENDING (a duplicate of an
+ *       entry admitted earlier lands here); active_p -> ALREADY_ACTIVE;
+ *       else pending_p = 1, capacity - 1 -> OK: the caller dials these.
+ * Two deliberate differences from the reference.  Its event loop applies events in arrival order;
+ * a round applies frees first, then incoming, then dials: a caller who needs another interleaving
+ * makes several calls, and a round with one non-empty list is exactly that event type.  Its dial
+ * loop breaks at ErrTorrentAtCapacity; here every remaining entry gets its status, and the state is
+ * the same because capacity == 0 is AddPending's first check.
+ *
+ * Every output element is stored by the call, the caller pre-zeroes nothing: one status an entry
+ * of each list (at the list's offset), n_admitted_out[2t] (incoming) and [2t + 1] (dials),
+ * n_freed_out[t].  bits, expiry and capacity are read and written.  KRK_EINVAL, refused before any
+ * output, bit, expiry or capacity is touched: P >= 2^30, a peer >= P in any list, a self_peer that
+ * is neither < P nor KRK_CN_NONE, an unknown kind or flag bit, a reserved field that is not 0,
+ * transitions that do not ascend strictly, now < 0, blacklist_duration < 0 or their sum past
+ * INT64_MAX, a neighbour row that runs past n_neighbor_words, an offset >= 2^48, a NULL that is not
+ * nullable (a pointer nothing is read from or stored to may be NULL), and in the host form a
+ * capacity >= 2^31.  KRK_ERANGE: a list of 2^32 entries or more.  n_torrents == 0 is KRK_OK.  The
+ * regions the torrents name in one array must not overlap. */
+#define KRK_CN_NONE 0xFFFFFFFFu                /* self_peer: we are not among the torrent's peers */
+#define KRK_CN_NO_ROW 0xFFFFFFFFFFFFFFFFull    /* neigh_off: no neighbours */
+#define KRK_CN_TORRENT_COMPLETE 1u             /* krk_conn_torrent.flags: dispatcher.Complete() */
+#define KRK_CN_DISABLE_BLACKLIST 1u            /* a round's flags: Config.DisableBlacklist */
+#define KRK_CN_ESTABLISHED 0u                  /* krk_conn_transition.kind */
+#define KRK_CN_FAILED_IN 1u
+#define KRK_CN_FAILED_OUT 2u
+#define KRK_CN_CLOSED 3u
+#define KRK_CN_OK 0x001u                       /* status bits */
+#define KRK_CN_FREED 0x002u
+#define KRK_CN_NOOP 0x004u
+#define KRK_CN_NOT_PENDING 0x008u              /* ErrInvalidActiveTransition */
+#define KRK_CN_BLACKLISTED_NOW 0x010u
+#define KRK_CN_STILL_BLACKLISTED 0x020u        /* "conn is already blacklisted" */
+#define KRK_CN_AT_CAPACITY 0x040u              /* ErrTorrentAtCapacity */
+#define KRK_CN_ALREADY_PENDING 0x080u          /* ErrConnAlreadyPending */
+#define KRK_CN_ALREADY_ACTIVE 0x100u           /* ErrConnAlreadyActive */
+#define KRK_CN_TOO_MANY_MUTUAL 0x200u          /* ErrTooManyMutualConns */
+#define KRK_CN_SELF 0x400u
+#define KRK_CN_BLACKLISTED 0x800u
+#define KRK_CN_TORRENT_IS_COMPLETE 0x1000u
+typedef struct {
+    uint32_t n_peers;   /* P */
+    uint32_t self_peer; /* our own index among the torrent's peers, or KRK_CN_NONE */
+    uint32_t flags;     /* KRK_CN_TORRENT_COMPLETE */
+    uint32_t reserved;  /* 0 */
+    uint64_t bits_off;  /* first word of the active row in `bits`; the pending row follows */
+    uint64_t peer_off;  /* first entry in expiry (a round) / created, received, sent (a sweep) */
+    uint64_t close_off; /* first word of the close row in close_out: krk_conn_preempt only */
+} krk_conn_torrent;
+typedef struct {
+    uint64_t trans_off, n_trans; /* first entry in `transitions` and in trans_status_out */
+    uint64_t in_off, n_in;       /* ... in `incoming` and in in_status_out */
+    uint64_t dial_off, n_dial;   /* ... in `dials` and in dial_status_out */
+} krk_conn_lists;                /* parallel to torrents[] */
+typedef struct {
+    uint32_t peer;
+    uint32_t kind; /* KRK_CN_ESTABLISHED .. KRK_CN_CLOSED */
+} krk_conn_transition;
+typedef struct {
+    uint32_t peer;
+    uint32_t reserved;  /* 0 */
+    uint64_t neigh_off; /* word offset of the WP-word row in `neighbors`, or KRK_CN_NO_ROW */
+} krk_conn_incoming;
+/* The whole round of n_torrents torrents on the host.  No device. */
+int krk_conn_round(const krk_conn_torrent* torrents, const krk_conn_lists* lists, uint64_t n_torrents, uint64_t* bits,
+                   int64_t* expiry, uint32_t* capacity, const krk_conn_transition* transitions,
+                   const krk_conn_incoming* incoming, const uint32_t* dials, const uint64_t* neighbors,
+                   uint64_t n_neighbor_words, int64_t now, int64_t blacklist_duration, uint32_t max_mutual,
+                   uint32_t flags, uint32_t* trans_status_out, uint32_t* in_status_out, uint32_t* dial_status_out,
+                   uint32_t* n_admitted_out, uint32_t* n_freed_out);
+/* The same on the device (conn_round.hip), bit for bit -- rows, expiries, capacities and every
+ * output; asynchronous on `stream`: one launch, one wave a torrent.  bits_dev, expiry_dev,
+ * capacity_dev, neighbors_dev and the outputs are device memory or page-locked host memory
+ * (krk_host_alloc), the 64-bit arrays 8-byte and the others 4-byte aligned: anything else is
+ * KRK_EINVAL before anything is launched.  The torrents and the three lists are host memory,
+ * checked as above and copied into the library's staging before the call returns.  The capacities
+ * cannot be read before the launch and are trusted to be below 2^31.  KRK_ERANGE: 2^31 torrents or
+ * more.  KRK_ENODEV without a gfx950 device: there is no fall-back to the host form. */
+int krk_conn_round_dev(const krk_conn_torrent* torrents_host, const krk_conn_lists* lists_host, uint64_t n_torrents,
+                       uint64_t* bits_dev, int64_t* expiry_dev, uint32_t* capacity_dev,
+                       const krk_conn_transition* transitions_host, const krk_conn_incoming* incoming_host,
+                       const uint32_t* dials_host, const uint64_t* neighbors_dev, uint64_t n_neighbor_words, int64_t now,
+                       int64_t blacklist_duration, uint32_t max_mutual, uint32_t flags, uint32_t* trans_status_out,
+                       uint32_t* in_status_out, uint32_t* dial_status_out, uint32_t* n_admitted_out,
+                       uint32_t* n_freed_out, void* stream);
+/* The preemption tick's connection half (preemptionTickEvent, events.go:370-392), element-wise:
+ * peer p of torrent t is closed iff active_p and either
+ *   now - max(created_p, received_p, sent_p) > conn_tti   (idle; timeutil.MostRecent is a max)
+ *   or now - created_p > conn_ttl                          (expired); both strict, as the reference.
+ * The three int64 arrays (CreatedAt, LastGoodPieceReceived, LastPieceSent) are indexed from
+ * peer_off; 0 is "never", and a negative time counts as 0.  Only the active row of `bits` is read;
+ * self_peer and flags are not.  Stored: close_out[close_off + w] for every word of the row (tail
+ * bits 0) and n_close_out[t].  KRK_EINVAL before anything is touched: P >= 2^30, an offset >= 2^48,
+ * a non-zero reserved, a negative now, conn_tti or conn_ttl, a NULL that is not nullable.  The
+ * torrent-idle half of the tick is one comparison a torrent and stays with the caller. */
+int krk_conn_preempt(const krk_conn_torrent* torrents, uint64_t n_torrents, const uint64_t* bits, const int64_t* created,
+                     const int64_t* received, const int64_t* sent, int64_t now, int64_t conn_tti, int64_t conn_ttl,
+                     uint64_t* close_out, uint32_t* n_close_out);
+/* The same on the device (conn_round.hip), bit for bit; asynchronous on `stream`: one launch, one
+ * workgroup a torrent, one lane a peer.  The arrays are device or page-locked host memory, the
+ * 64-bit ones 8-byte and n_close_out 4-byte aligned; KRK_ENODEV without a gfx950 device. */
+int krk_conn_preempt_dev(const krk_conn_torrent* torrents_host, uint64_t n_torrents, const uint64_t* bits_dev,
+                         const int64_t* created_dev, const int64_t* received_dev, const int64_t* sent_dev, int64_t now,
+                         int64_t conn_tti, int64_t conn_ttl, uint64_t* close_out, uint32_t* n_close_out, void* stream);
+
 /* ------------------------------------------- re-piece stored MetaInfo, no blob read
  * The piece sums of a stored MetaInfo at a COARSER piece length, from the stored sums alone:
  * what a changed piece-length table (lib/metainfogen/config.go:48-80) asks of every

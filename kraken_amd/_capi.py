@@ -23,6 +23,11 @@ KRK_PR_EXPIRED, KRK_PR_UNSENT, KRK_PR_INVALID = 1, 2, 3
 KRK_AN_MAX_WINDOWS, KRK_AN_MAX_ORIGINS, KRK_AN_MAX_LIMIT = 8, 8, 64
 KRK_AN_DEFAULT, KRK_AN_COMPLETENESS, KRK_AN_COMPLETE = 0, 1, 1
 KRK_AN_NONE, KRK_AN_ORIGIN, KRK_AN_COMPLETE_BIT = 0xFFFFFFFF, 0x80000000, 0x40000000
+KRK_CN_NONE, KRK_CN_NO_ROW, KRK_CN_TORRENT_COMPLETE, KRK_CN_DISABLE_BLACKLIST = 0xFFFFFFFF, 0xFFFFFFFFFFFFFFFF, 1, 1
+KRK_CN_ESTABLISHED, KRK_CN_FAILED_IN, KRK_CN_FAILED_OUT, KRK_CN_CLOSED = 0, 1, 2, 3
+(KRK_CN_OK, KRK_CN_FREED, KRK_CN_NOOP, KRK_CN_NOT_PENDING, KRK_CN_BLACKLISTED_NOW, KRK_CN_STILL_BLACKLISTED,
+ KRK_CN_AT_CAPACITY, KRK_CN_ALREADY_PENDING, KRK_CN_ALREADY_ACTIVE, KRK_CN_TOO_MANY_MUTUAL, KRK_CN_SELF,
+ KRK_CN_BLACKLISTED, KRK_CN_TORRENT_IS_COMPLETE) = (1 << k for k in range(13))
 
 
 class KrakenError(RuntimeError):
@@ -77,6 +82,24 @@ class krk_announce_torrent(C.Structure):
 class krk_announce(C.Structure):
     _fields_ = [("torrent", C.c_uint32), ("peer", C.c_uint32), ("flags", C.c_uint32), ("source", C.c_uint32),
                 ("seed", C.c_uint64)]
+
+
+class krk_conn_torrent(C.Structure):
+    _fields_ = [("n_peers", C.c_uint32), ("self_peer", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32),
+                ("bits_off", C.c_uint64), ("peer_off", C.c_uint64), ("close_off", C.c_uint64)]
+
+
+class krk_conn_lists(C.Structure):
+    _fields_ = [("trans_off", C.c_uint64), ("n_trans", C.c_uint64), ("in_off", C.c_uint64), ("n_in", C.c_uint64),
+                ("dial_off", C.c_uint64), ("n_dial", C.c_uint64)]
+
+
+class krk_conn_transition(C.Structure):
+    _fields_ = [("peer", C.c_uint32), ("kind", C.c_uint32)]
+
+
+class krk_conn_incoming(C.Structure):
+    _fields_ = [("peer", C.c_uint32), ("reserved", C.c_uint32), ("neigh_off", C.c_uint64)]
 
 
 class krk_chunk(C.Structure):
@@ -161,6 +184,16 @@ def _load() -> C.CDLL:
                                    C.c_uint32, C.c_uint32, u32p, u32p, u32p]),
         "krk_announce_round_dev": (i, [C.POINTER(krk_announce_torrent), C.c_uint64, vp, C.POINTER(krk_announce), C.c_uint64,
                                        C.c_uint32, C.c_uint32, vp, vp, vp, vp]),
+        "krk_conn_round": (i, [C.POINTER(krk_conn_torrent), C.POINTER(krk_conn_lists), C.c_uint64, vp, vp, vp,
+                               C.POINTER(krk_conn_transition), C.POINTER(krk_conn_incoming), vp, vp, C.c_uint64, C.c_int64,
+                               C.c_int64, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp]),
+        "krk_conn_round_dev": (i, [C.POINTER(krk_conn_torrent), C.POINTER(krk_conn_lists), C.c_uint64, vp, vp, vp,
+                                   C.POINTER(krk_conn_transition), C.POINTER(krk_conn_incoming), vp, vp, C.c_uint64,
+                                   C.c_int64, C.c_int64, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp]),
+        "krk_conn_preempt": (i, [C.POINTER(krk_conn_torrent), C.c_uint64, vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_int64,
+                                 vp, vp]),
+        "krk_conn_preempt_dev": (i, [C.POINTER(krk_conn_torrent), C.c_uint64, vp, vp, vp, vp, C.c_int64, C.c_int64,
+                                     C.c_int64, vp, vp, vp]),
         "krk_repiece_sums": (i, [u32p, C.c_uint64, C.c_int64, C.c_int64, C.c_int64, u32p, C.c_uint64]),
         "krk_repiece_batch": (i, [C.POINTER(krk_repiece_blob), C.c_uint64, u32p, u32p]),
         "krk_repiece_batch_dev": (i, [C.POINTER(krk_repiece_blob), C.c_uint64, vp, vp, vp]),

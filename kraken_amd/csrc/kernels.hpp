@@ -426,6 +426,43 @@ hipError_t launch_announce_round(const an::Torrent* tors, const an::Announce* an
                                  uint32_t limit, uint32_t policy, uint32_t* handout, uint32_t* n_out, uint32_t* labels,
                                  hipStream_t s);
 
+// ---------------------------------------------------------------- connection rounds
+// One torrent of a connection round (conn_round.hip, conn_math.hpp): its active and pending rows
+// at bits[bits_off ..], its expiries at expiry[peer_off ..], its capacity at capacity[t]; its three
+// lists in the staged arrays from tr_at / in_at / dial_at, their statuses from trans_off / in_off /
+// dial_off of the three status outputs.
+namespace cn {
+struct Transition;
+struct Incoming;
+struct Round;
+}
+struct alignas(16) CnTorrent {
+    uint64_t bits_off, peer_off;
+    uint64_t tr_at, trans_off, n_trans;
+    uint64_t in_at, in_off, n_in;
+    uint64_t dial_at, dial_off, n_dial;
+    uint32_t n_peers, self_peer, flags, pad;
+    uint64_t pad2;
+};
+static_assert(sizeof(CnTorrent) == 112, "CnTorrent layout");
+// One wave64 a torrent runs the three phases in order: every status, n_admitted[2t], [2t + 1],
+// n_freed[t] and capacity[t] stored.  The lists are valid (cn::lists_error).
+hipError_t launch_conn_round(const CnTorrent* tors, uint64_t n_tors, const cn::Transition* tr, const cn::Incoming* in,
+                             const uint32_t* dial, const uint64_t* neighbors, uint64_t* bits, int64_t* expiry,
+                             uint32_t* capacity, const cn::Round& round, uint32_t* tr_st, uint32_t* in_st, uint32_t* dial_st,
+                             uint32_t* n_admitted, uint32_t* n_freed, hipStream_t s);
+// One torrent of a preemption sweep: its active row, its three time arrays from peer_off, its
+// close row at close[close_off ..].
+struct alignas(16) CnSweep {
+    uint64_t bits_off, peer_off, close_off;
+    uint32_t n_peers, pad;
+};
+static_assert(sizeof(CnSweep) == 32, "CnSweep layout");
+// One workgroup a torrent: every word of its close row and n_close[t] stored.
+hipError_t launch_conn_preempt(const CnSweep* tors, uint64_t n_tors, const uint64_t* bits, const int64_t* created,
+                               const int64_t* received, const int64_t* sent, int64_t now, int64_t tti, int64_t ttl,
+                               uint64_t* close, uint32_t* n_close, hipStream_t s);
+
 // ---------------------------------------------------------------- synthetic data
 // One synthetic chunk: bytes [offset, offset + n) of the blob whose stream seed is `seed`.
 struct SynthChunk {

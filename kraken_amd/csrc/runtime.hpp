@@ -73,11 +73,11 @@ struct Event {
 };
 
 // ------------------------------------------------------------------ timing
-enum Kern { K_CRC, K_SHA, K_HRW, K_FILTER, K_GATHER, K_SYNTH, K_HOSTG, K_INFOHASH, K_BITFIELD, K_REPIECE, K_RSELECT, K_MJSER, K_MJPARSE, K_DHEXPARSE, K_DHEXFMT, K_CLEANPLAN, K_PIECEREQ, K_PIECERESEND, K_ANNOUNCE, K_N };
+enum Kern { K_CRC, K_SHA, K_HRW, K_FILTER, K_GATHER, K_SYNTH, K_HOSTG, K_INFOHASH, K_BITFIELD, K_REPIECE, K_RSELECT, K_MJSER, K_MJPARSE, K_DHEXPARSE, K_DHEXFMT, K_CLEANPLAN, K_PIECEREQ, K_PIECERESEND, K_ANNOUNCE, K_CONNROUND, K_CONNPREEMPT, K_N };
 inline const char* kKernNames[K_N] = {"crc32_pieces", "sha256_multi", "hrw_order", "ring_filter",    "hrw_gather",
                                       "synth_fill",   "host_gather",  "info_hash", "piece_bitfield", "piece_repiece",
                                       "ring_select",  "metainfo_serialize", "metainfo_parse", "digest_parse_hex", "digest_format_hex",
-                                      "cleanup_plan", "piece_request", "piece_resend", "announce_round"};
+                                      "cleanup_plan", "piece_request", "piece_resend", "announce_round", "conn_round", "conn_preempt"};
 inline std::atomic<bool> g_timing{false};
 struct Pending {
     hipEvent_t a, b;

@@ -8,7 +8,8 @@ import os
 import numpy as np
 
 from ._capi import (check, krk_blob, krk_file_blob, krk_chunk, krk_launch_rec, krk_nodes, krk_planner_rates,
-                    krk_request_torrent, krk_resend_torrent, krk_failed_request, krk_announce_torrent, krk_announce, lib)
+                    krk_request_torrent, krk_resend_torrent, krk_failed_request, krk_announce_torrent, krk_announce, krk_conn_torrent,
+                    krk_conn_lists, krk_conn_transition, krk_conn_incoming, lib)
 
 ALIGN = 256  # every blob starts 256-byte aligned in the arena
 
@@ -1130,6 +1131,168 @@ def announce_round_dev(batch: AnnounceBatch, bits_dev, limit: int, policy: int =
         return out
     check(lib.krk_stream_sync(stream))
     return dst.to_host()
+
+
+CN_NONE, CN_NO_ROW, CN_TORRENT_COMPLETE, CN_DISABLE_BLACKLIST = 0xFFFFFFFF, 0xFFFFFFFFFFFFFFFF, 1, 1
+CN_ESTABLISHED, CN_FAILED_IN, CN_FAILED_OUT, CN_CLOSED = 0, 1, 2, 3
+(CN_OK, CN_FREED, CN_NOOP, CN_NOT_PENDING, CN_BLACKLISTED_NOW, CN_STILL_BLACKLISTED, CN_AT_CAPACITY, CN_ALREADY_PENDING,
+ CN_ALREADY_ACTIVE, CN_TOO_MANY_MUTUAL, CN_SELF, CN_BLACKLISTED, CN_TORRENT_IS_COMPLETE) = (1 << k for k in range(13))
+
+
+class ConnBatch:
+    """The torrents and lists of a connection round (or the torrents of a preemption sweep).
+    torrents: (n_peers, self_peer, flags) each; their states are packed back to back: torrent t's
+    active and pending rows from word .bits_off[t] of `bits`, its expiries (and a sweep's times) from
+    .peer_off[t], its close row from word .close_off[t].  lists: per torrent (transitions
+    [(peer, kind)], incoming [(peer, neighbour row or None)], dials [peer]), a neighbour row being
+    krk_bitfield_words(n_peers) uint64 words; None: no lists (a sweep).  .structs / .lists /
+    .transitions / .incoming are the C arrays, .dials and .neighbors numpy arrays."""
+
+    def __init__(self, torrents, lists=None):
+        torrents = [tuple(int(x) for x in t) for t in torrents]
+        k = len(torrents)
+        lists = [((), (), ())] * k if lists is None else [tuple(list(x) for x in l) for l in lists]
+        if len(lists) != k:
+            raise ValueError(f"ConnBatch: {len(lists)} lists for {k} torrents")
+        wp = [(p + 63) // 64 for p, _, _ in torrents]
+        self.bits_off, self.peer_off, self.close_off = (np.zeros(k + 1, dtype=np.uint64) for _ in range(3))
+        self.bits_off[1:] = np.cumsum([2 * w for w in wp])
+        self.peer_off[1:] = np.cumsum([p for p, _, _ in torrents])
+        self.close_off[1:] = np.cumsum(wp)
+        self.total_words, self.total_peers, self.close_words = int(self.bits_off[-1]), int(self.peer_off[-1]), int(self.close_off[-1])
+        self.n_torrents = k
+        self.structs = (krk_conn_torrent * max(k, 1))()
+        self.lists = (krk_conn_lists * max(k, 1))()
+        nt, ni, nd = (sum(len(l[j]) for l in lists) for j in range(3))
+        self.n_trans, self.n_in, self.n_dial = nt, ni, nd
+        self.transitions = (krk_conn_transition * max(nt, 1))()
+        self.incoming = (krk_conn_incoming * max(ni, 1))()
+        self.dials = np.zeros(max(nd, 1), dtype=np.uint32)
+        self.list_off = np.zeros((k + 1, 3), dtype=np.uint64)
+        rows, at, a = [], 0, [0, 0, 0]
+        for t, ((p, me, flags), (tr, inc, dial)) in enumerate(zip(torrents, lists)):
+            self.structs[t] = krk_conn_torrent(p, me, flags, 0, int(self.bits_off[t]), int(self.peer_off[t]),
+                                               int(self.close_off[t]))
+            self.lists[t] = krk_conn_lists(a[0], len(tr), a[1], len(inc), a[2], len(dial))
+            for peer, kind in tr:
+                self.transitions[a[0]] = krk_conn_transition(int(peer), int(kind))
+                a[0] += 1
+            for peer, row in inc:
+                if row is None:
+                    self.incoming[a[1]] = krk_conn_incoming(int(peer), 0, CN_NO_ROW)
+                else:
+                    row = np.ascontiguousarray(row, dtype=np.uint64)
+                    if row.size != wp[t]:
+                        raise ValueError(f"ConnBatch: a neighbour row of {row.size} words for {p} peers")
+                    self.incoming[a[1]] = krk_conn_incoming(int(peer), 0, at)
+                    rows.append(row)
+                    at += wp[t]
+                a[1] += 1
+            for peer in dial:
+                self.dials[a[2]] = int(peer)
+                a[2] += 1
+            self.list_off[t + 1] = a
+        self.neighbors = np.concatenate(rows) if rows else np.zeros(1, dtype=np.uint64)
+        self.n_neighbor_words = at
+
+    def __len__(self):
+        return self.n_torrents
+
+    def split(self, a: np.ndarray, t: int, which: int) -> np.ndarray:
+        """Torrent t's slice of a status array: which = 0 transitions, 1 incoming, 2 dials."""
+        return a[int(self.list_off[t, which]):int(self.list_off[t + 1, which])]
+
+
+class ConnOutputs:
+    """The outputs of conn_round_dev, in device memory or (pinned=True) in page-locked host memory:
+    .trans, .incoming, .dial (uint32 statuses an entry), .n_admitted (uint32, two a torrent),
+    .n_freed (uint32 a torrent)."""
+
+    def __init__(self, batch: ConnBatch, pinned: bool = False):
+        self.sizes = (batch.n_trans, batch.n_in, batch.n_dial, 2 * len(batch), len(batch))
+        self.pinned = pinned
+        make = (lambda k: PinnedArray((max(k, 1),), np.uint32)) if pinned else (lambda k: DeviceBuffer(max(k, 1) * 4))
+        self.trans, self.incoming, self.dial, self.n_admitted, self.n_freed = (make(k) for k in self.sizes)
+
+    def buffers(self):
+        return self.trans, self.incoming, self.dial, self.n_admitted, self.n_freed
+
+    def fill(self, byte: int):
+        """Every output byte set to `byte` (tests: the call must overwrite all of it)."""
+        for b in self.buffers():
+            if self.pinned:
+                b.a.view(np.uint8)[:] = byte
+            else:
+                b.from_host(np.full(b.nbytes, byte, dtype=np.uint8))
+
+    def to_host(self):
+        """(trans, incoming, dial, n_admitted (T, 2), n_freed) as numpy arrays, once the stream has run."""
+        got = [b.a[:k].copy() if self.pinned else b.to_host(np.uint32, k) for b, k in zip(self.buffers(), self.sizes)]
+        got[3] = got[3].reshape(-1, 2)
+        return tuple(got)
+
+
+def conn_round(batch: ConnBatch, bits, expiry, capacity, now: int, blacklist_duration: int, max_mutual: int, flags: int = 0):
+    """krk_conn_round: the whole connection round on the host.  bits (uint64), expiry (int64) and
+    capacity (uint32) are contiguous arrays in the batch's layout, UPDATED IN PLACE.  Returns
+    (transition, incoming and dial statuses, n_admitted (T, 2), n_freed)."""
+    for a, t, n, what in ((bits, np.uint64, batch.total_words, "bits"), (expiry, np.int64, batch.total_peers, "expiry"),
+                          (capacity, np.uint32, len(batch), "capacity")):
+        if not (isinstance(a, np.ndarray) and a.dtype == t and a.flags.c_contiguous and a.size >= n):
+            raise ValueError(f"conn_round: {what} must be a contiguous {np.dtype(t).name} array of at least {n}")
+    outs = [np.zeros(max(k, 1), dtype=np.uint32) for k in (batch.n_trans, batch.n_in, batch.n_dial, 2 * len(batch), len(batch))]
+    check(lib.krk_conn_round(batch.structs, batch.lists, len(batch), bits.ctypes.data, expiry.ctypes.data,
+                             capacity.ctypes.data, batch.transitions, batch.incoming, batch.dials.ctypes.data,
+                             batch.neighbors.ctypes.data, batch.n_neighbor_words, now, blacklist_duration, max_mutual, flags,
+                             *(o.ctypes.data for o in outs)))
+    return (outs[0][:batch.n_trans], outs[1][:batch.n_in], outs[2][:batch.n_dial],
+            outs[3][:2 * len(batch)].reshape(-1, 2), outs[4][:len(batch)])
+
+
+def conn_round_dev(batch: ConnBatch, bits_dev, expiry_dev, capacity_dev, neighbors_dev, now: int, blacklist_duration: int,
+                   max_mutual: int, flags: int = 0, out: ConnOutputs | None = None, stream=None):
+    """krk_conn_round_dev: the round in one launch on the device.  bits_dev / expiry_dev /
+    capacity_dev: DeviceBuffer or PinnedArray in the batch's layout, updated in place;
+    neighbors_dev: the batch's .neighbors in device or page-locked memory (None: uploaded here).
+    out: ConnOutputs to fill asynchronously on `stream` (returned); None: the host form's tuple,
+    returned once the stream has run the call."""
+    if neighbors_dev is None and batch.n_neighbor_words:
+        neighbors_dev = DeviceBuffer(batch.neighbors.nbytes)
+        neighbors_dev.from_host(batch.neighbors)
+    dst = ConnOutputs(batch, pinned=True) if out is None else out
+    check(lib.krk_conn_round_dev(batch.structs, batch.lists, len(batch), bits_dev.ptr, expiry_dev.ptr, capacity_dev.ptr,
+                                 batch.transitions, batch.incoming, batch.dials.ctypes.data,
+                                 neighbors_dev.ptr if neighbors_dev is not None else None, batch.n_neighbor_words, now,
+                                 blacklist_duration, max_mutual, flags, *(b.ptr for b in dst.buffers()), stream))
+    if out is not None:
+        return out
+    check(lib.krk_stream_sync(stream))
+    return dst.to_host()
+
+
+def conn_preempt(batch: ConnBatch, bits, created, received, sent, now: int, conn_tti: int, conn_ttl: int):
+    """krk_conn_preempt on the host: (close rows packed at .close_off, n_close a torrent)."""
+    b = np.ascontiguousarray(bits, dtype=np.uint64)
+    times = [np.ascontiguousarray(a, dtype=np.int64) for a in (created, received, sent)]
+    if b.size < batch.total_words or any(a.size < batch.total_peers for a in times):
+        raise ValueError("conn_preempt: bits or times shorter than the batch's layout")
+    close = np.zeros(max(batch.close_words, 1), dtype=np.uint64)
+    n_close = np.zeros(max(len(batch), 1), dtype=np.uint32)
+    check(lib.krk_conn_preempt(batch.structs, len(batch), b.ctypes.data, *(a.ctypes.data for a in times), now, conn_tti,
+                               conn_ttl, close.ctypes.data, n_close.ctypes.data))
+    return close[:batch.close_words], n_close[:len(batch)]
+
+
+def conn_preempt_dev(batch: ConnBatch, bits_dev, created_dev, received_dev, sent_dev, now: int, conn_tti: int,
+                     conn_ttl: int, stream=None):
+    """krk_conn_preempt_dev: the sweep on the device over arrays in device or page-locked memory;
+    returns the host form's tuple once the stream has run the call."""
+    close = PinnedArray((max(batch.close_words, 1),), np.uint64)
+    n_close = PinnedArray((max(len(batch), 1),), np.uint32)
+    check(lib.krk_conn_preempt_dev(batch.structs, len(batch), bits_dev.ptr, created_dev.ptr, received_dev.ptr, sent_dev.ptr,
+                                   now, conn_tti, conn_ttl, close.ptr, n_close.ptr, stream))
+    check(lib.krk_stream_sync(stream))
+    return close.a[:batch.close_words].copy(), n_close.a[:len(batch)].copy()
 
 
 class KernelTimer:
