@@ -323,6 +323,49 @@ inline uint64_t file_readahead_bytes() {
     return (v ? strtoull(v, nullptr, 10) : 0) << 20;
 }
 
+// O_DIRECT reads land in the pinned windows by the disk's DMA only where the kernel can pin
+// the windows' pages itself.  Where the runtime backs page-locked memory with device-mapped
+// pages (a GPU passed through to a virtual machine), the read is refused with EFAULT before
+// a byte moves: from the first such refusal on, the process reads O_DIRECT into an ordinary
+// page-aligned buffer of the reading thread and copies into the window -- still no page
+// cache, one host copy more.
+inline std::atomic<bool>& direct_reads_bounce() {
+    static std::atomic<bool> on{false};
+    return on;
+}
+
+// pread of a block-aligned request on an O_DIRECT descriptor into a pinned window.
+inline ssize_t direct_pread(int fd, uint8_t* dst, size_t want, off_t off) {
+    if (!direct_reads_bounce().load(std::memory_order_relaxed)) {
+        const ssize_t got = pread(fd, dst, want, off);
+        if (!(got < 0 && errno == EFAULT)) return got;
+        direct_reads_bounce().store(true, std::memory_order_relaxed);
+    }
+    constexpr size_t kBounce = size_t(1) << 20;
+    struct Bounce {
+        void* p = nullptr;
+        ~Bounce() { free(p); }
+    };
+    static thread_local Bounce bounce;
+    if (!bounce.p && posix_memalign(&bounce.p, 4096, kBounce) != 0) {
+        bounce.p = nullptr;
+        errno = ENOMEM;
+        return -1;
+    }
+    size_t done = 0;
+    while (done < want) {
+        const size_t ask = std::min(kBounce, want - done);
+        const ssize_t got = pread(fd, bounce.p, ask, off + (off_t)done);
+        if (got < 0 && errno == EINTR) continue;
+        if (got < 0 && !done) return -1;
+        if (got <= 0) break;  // what is in so far; the caller's next read meets the error or EOF
+        memcpy(dst + done, bounce.p, (size_t)got);
+        done += (size_t)got;
+        if ((size_t)got < ask) break;
+    }
+    return (ssize_t)done;
+}
+
 // Returns -1 on success, else the index of the failed task; err = its errno (0 = EOF).
 inline long par_read(const std::vector<ReadTask>& tasks, bool direct, int* err) {
     // Spans are cut in a stream of the tasks laid end to end, each padded to 4 KiB
@@ -351,7 +394,8 @@ inline long par_read(const std::vector<ReadTask>& tasks, bool direct, int* err) 
             while (a < b) {
                 size_t want = b - a;
                 if (direct) want = (want + 4095) & ~size_t(4095);
-                const ssize_t got = pread(t.fd, t.dst + a, want, (off_t)(t.off + a));
+                const ssize_t got = direct ? direct_pread(t.fd, t.dst + a, want, (off_t)(t.off + a))
+                                           : pread(t.fd, t.dst + a, want, (off_t)(t.off + a));
                 if (got < 0 && errno == EINTR) continue;
                 if (got <= 0) {
                     long expect = -1;
@@ -427,6 +471,8 @@ class AioReader {
     long read(const std::vector<ReadTask>& tasks, int* err) {
         *err = 0;
         if (tasks.empty()) return -1;
+        // the windows take no O_DIRECT reads here (direct_pread): the caller's threads read
+        if (direct_reads_bounce().load(std::memory_order_relaxed)) return -2;
         if (!ctx_ && (failed_ || !(ctx_ = AioContexts::get().take(kAioDepth)))) {
             failed_ = true;
             return -2;
@@ -479,7 +525,10 @@ class AioReader {
                 const ReadTask& t = tasks[task_of[q]];
                 const int64_t res = ev[e].res;
                 if (bad < 0) {
-                    if (res < 0) {
+                    if (res == -EFAULT) {  // the window's pages refused: through the bounce buffer
+                        direct_reads_bounce().store(true, std::memory_order_relaxed);
+                        if (!sync_read(t, err)) bad = (long)task_of[q];
+                    } else if (res < 0) {
                         *err = (int)-res;
                         bad = (long)task_of[q];
                     } else if ((uint64_t)res < t.n && (res & 4095)) {  // the file ended inside the block
@@ -507,7 +556,7 @@ class AioReader {
     static bool sync_read(const ReadTask& t, int* err) {
         size_t a = 0;
         while (a < t.n) {
-            const ssize_t got = pread(t.fd, t.dst + a, ((t.n - a) + 4095) & ~size_t(4095), (off_t)(t.off + a));
+            const ssize_t got = direct_pread(t.fd, t.dst + a, ((t.n - a) + 4095) & ~size_t(4095), (off_t)(t.off + a));
             if (got < 0 && errno == EINTR) continue;
             if (got <= 0) {
                 *err = got < 0 ? errno : 0;
