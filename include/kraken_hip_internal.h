@@ -139,6 +139,15 @@ int krk_sha_tail_plan(const uint64_t* lengths, uint64_t n, int threads, uint32_t
  * KRK_FILE_DIRECT says otherwise), else -1; and whether it read with O_DIRECT. */
 int krk_windows_last_phases(double* loop_s, double* acquire_s, double* fill_s, double* enqueue_s,
                             double* resident, int* direct_reads);
+/* The calling thread's last file batch (krk_metainfo_digest_files, krk_piece_sums_files on the
+ * GPU placement): which way its bytes came, the first n of counts[9] = files opened O_DIRECT,
+ * files that wanted O_DIRECT and were opened buffered, bytes read O_DIRECT straight into a
+ * window, bytes read O_DIRECT through the bounce buffer, the bounce loop's preads, bytes read
+ * through the page cache, AIO requests reaped, tasks the AIO reader read synchronously (not
+ * submitted, short on a block edge, or refused), and whether the process read through the
+ * bounce buffer when the call returned.  Bytes are those delivered, not the block-rounded
+ * requests: after a call that succeeds the three byte counts add up to the files' lengths. */
+int krk_windows_last_reads(uint64_t* counts, int n);
 /* The gather of host-buffer calls, process-wide: -1 AUTO (the default: page-locked blobs
  * gathered in wide windows, pageable ones staged -- measured faster), 0 off
  * (stage every window through the pinned host windows), 1 on (pageable blobs registered for

@@ -288,6 +288,9 @@ int krk_host_alloc(uint64_t bytes, void** out) {
             munmap(p, len);
         }
     }
+    // Below 2 MiB a block is plain hipHostMalloc memory, as the staging windows are: the tests ask this
+    // machine whether such pages take an O_DIRECT read by reading into one (tests/window_matrix.py
+    // machine_refuses).  Pooling or registering small blocks another way would make that probe lie.
     hipError_t e = hipHostMalloc(out, bytes ? bytes : 1, hipHostMallocDefault);
     KRK_CHECK(e == hipSuccess, KRK_ENOMEM, "hipHostMalloc(%llu): %s", (unsigned long long)bytes,
               hipGetErrorString(e));

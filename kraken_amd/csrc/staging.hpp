@@ -12,6 +12,7 @@
 #include <cstring>
 #include <unordered_map>
 
+#include "direct_read.hpp"
 #include "runtime.hpp"
 #include "window_math.hpp"
 
@@ -323,51 +324,9 @@ inline uint64_t file_readahead_bytes() {
     return (v ? strtoull(v, nullptr, 10) : 0) << 20;
 }
 
-// O_DIRECT reads land in the pinned windows by the disk's DMA only where the kernel can pin
-// the windows' pages itself.  Where the runtime backs page-locked memory with device-mapped
-// pages (a GPU passed through to a virtual machine), the read is refused with EFAULT before
-// a byte moves: from the first such refusal on, the process reads O_DIRECT into an ordinary
-// page-aligned buffer of the reading thread and copies into the window -- still no page
-// cache, one host copy more.
-inline std::atomic<bool>& direct_reads_bounce() {
-    static std::atomic<bool> on{false};
-    return on;
-}
-
-// pread of a block-aligned request on an O_DIRECT descriptor into a pinned window.
-inline ssize_t direct_pread(int fd, uint8_t* dst, size_t want, off_t off) {
-    if (!direct_reads_bounce().load(std::memory_order_relaxed)) {
-        const ssize_t got = pread(fd, dst, want, off);
-        if (!(got < 0 && errno == EFAULT)) return got;
-        direct_reads_bounce().store(true, std::memory_order_relaxed);
-    }
-    constexpr size_t kBounce = size_t(1) << 20;
-    struct Bounce {
-        void* p = nullptr;
-        ~Bounce() { free(p); }
-    };
-    static thread_local Bounce bounce;
-    if (!bounce.p && posix_memalign(&bounce.p, 4096, kBounce) != 0) {
-        bounce.p = nullptr;
-        errno = ENOMEM;
-        return -1;
-    }
-    size_t done = 0;
-    while (done < want) {
-        const size_t ask = std::min(kBounce, want - done);
-        const ssize_t got = pread(fd, bounce.p, ask, off + (off_t)done);
-        if (got < 0 && errno == EINTR) continue;
-        if (got < 0 && !done) return -1;
-        if (got <= 0) break;  // what is in so far; the caller's next read meets the error or EOF
-        memcpy(dst + done, bounce.p, (size_t)got);
-        done += (size_t)got;
-        if ((size_t)got < ask) break;
-    }
-    return (ssize_t)done;
-}
-
-// Returns -1 on success, else the index of the failed task; err = its errno (0 = EOF).
-inline long par_read(const std::vector<ReadTask>& tasks, bool direct, int* err) {
+// Returns -1 on success, else the index of the failed task; err = its errno (0 = EOF).  rc
+// (or null) counts the bytes by the way they came (direct_read.hpp).
+inline long par_read(const std::vector<ReadTask>& tasks, bool direct, int* err, ReadCounts* rc = nullptr) {
     // Spans are cut in a stream of the tasks laid end to end, each padded to 4 KiB
     // when direct, so every span boundary falls on a block boundary of its task.
     size_t total = 0;
@@ -394,8 +353,9 @@ inline long par_read(const std::vector<ReadTask>& tasks, bool direct, int* err) 
             while (a < b) {
                 size_t want = b - a;
                 if (direct) want = (want + 4095) & ~size_t(4095);
-                const ssize_t got = direct ? direct_pread(t.fd, t.dst + a, want, (off_t)(t.off + a))
+                const ssize_t got = direct ? direct_pread(t.fd, t.dst + a, want, (off_t)(t.off + a), rc, b - a)
                                            : pread(t.fd, t.dst + a, want, (off_t)(t.off + a));
+                if (rc && !direct && got > 0) rc->add(&ReadCounts::cached_bytes, (uint64_t)got);
                 if (got < 0 && errno == EINTR) continue;
                 if (got <= 0) {
                     long expect = -1;
@@ -468,7 +428,7 @@ class AioReader {
     ~AioReader() {
         if (ctx_ && !broken_) AioContexts::get().give(ctx_);  // nothing in flight: every read was reaped
     }
-    long read(const std::vector<ReadTask>& tasks, int* err) {
+    long read(const std::vector<ReadTask>& tasks, int* err, ReadCounts* rc = nullptr) {
         *err = 0;
         if (tasks.empty()) return -1;
         // the windows take no O_DIRECT reads here (direct_pread): the caller's threads read
@@ -507,7 +467,7 @@ class AioReader {
                 if (r < 0) r = 0;  // nothing went: the slots come back below
                 for (int k = (int)r; k < nsub; ++k) {  // not submitted: read them synchronously
                     const unsigned q = (unsigned)ptr[k]->aio_data;
-                    if (bad < 0 && !sync_read(tasks[task_of[q]], err)) bad = (long)task_of[q];
+                    if (bad < 0 && !sync_read(tasks[task_of[q]], err, rc)) bad = (long)task_of[q];
                     free_slot.push_back(q);
                 }
                 inflight += (size_t)r;
@@ -523,11 +483,16 @@ class AioReader {
             for (long e = 0; e < got; ++e) {
                 const unsigned q = (unsigned)ev[e].data;
                 const ReadTask& t = tasks[task_of[q]];
-                const int64_t res = ev[e].res;
+                int64_t res = ev[e].res;
+                if (rc) rc->add(&ReadCounts::aio_reaped, 1);
+                if (res >= 0 && direct_refuse_now()) {  // diag: as refused, and no byte of the file left behind
+                    memset(t.dst, kRefusedFiller, (size_t)cb[q].aio_nbytes);
+                    res = -EFAULT;
+                }
                 if (bad < 0) {
                     if (res == -EFAULT) {  // the window's pages refused: through the bounce buffer
                         direct_reads_bounce().store(true, std::memory_order_relaxed);
-                        if (!sync_read(t, err)) bad = (long)task_of[q];
+                        if (!sync_read(t, err, rc)) bad = (long)task_of[q];
                     } else if (res < 0) {
                         *err = (int)-res;
                         bad = (long)task_of[q];
@@ -535,11 +500,14 @@ class AioReader {
                         *err = 0;
                         bad = (long)task_of[q];
                     } else if ((uint64_t)res < t.n) {  // short on a block edge: the rest synchronously
+                        if (rc) rc->add(&ReadCounts::window_bytes, (uint64_t)res);
                         ReadTask rest = t;
                         rest.off += (uint64_t)res;
                         rest.dst += res;
                         rest.n -= (size_t)res;
-                        if (!sync_read(rest, err)) bad = (long)task_of[q];
+                        if (!sync_read(rest, err, rc)) bad = (long)task_of[q];
+                    } else if (rc) {
+                        rc->add(&ReadCounts::window_bytes, t.n);
                     }
                 }
                 free_slot.push_back(q);
@@ -553,10 +521,11 @@ class AioReader {
     aio_context_t ctx_ = 0;
     bool failed_ = false, broken_ = false;
     // pread until t.n bytes are in (block-rounded requests); false + *err on failure or EOF
-    static bool sync_read(const ReadTask& t, int* err) {
+    static bool sync_read(const ReadTask& t, int* err, ReadCounts* rc) {
+        if (rc) rc->add(&ReadCounts::aio_rereads, 1);
         size_t a = 0;
         while (a < t.n) {
-            const ssize_t got = direct_pread(t.fd, t.dst + a, ((t.n - a) + 4095) & ~size_t(4095), (off_t)(t.off + a));
+            const ssize_t got = direct_pread(t.fd, t.dst + a, ((t.n - a) + 4095) & ~size_t(4095), (off_t)(t.off + a), rc, t.n - a);
             if (got < 0 && errno == EINTR) continue;
             if (got <= 0) {
                 *err = got < 0 ? errno : 0;

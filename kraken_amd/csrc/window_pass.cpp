@@ -59,9 +59,15 @@ FileSource::FileSource(const krk_file_blob* f, uint64_t n, bool want_direct, boo
     : files_(f), direct_(want_direct), async_(async), fd_(n, -1), is_direct_(n, 0),
       ra_(async ? new std::atomic<uint64_t>[n]() : nullptr) {}
 
+thread_local uint64_t t_last_reads[kReadCountWords];
+
 FileSource::~FileSource() {
     for (int x : fd_)
         if (x >= 0) close(x);
+    const std::atomic<uint64_t>* c[] = {&rc_.direct_files, &rc_.buffered_files, &rc_.window_bytes, &rc_.bounce_bytes,
+                                        &rc_.bounce_preads, &rc_.cached_bytes,  &rc_.aio_reaped,   &rc_.aio_rereads};
+    for (int k = 0; k < kReadCountWords - 1; ++k) t_last_reads[k] = c[k]->load(std::memory_order_relaxed);
+    t_last_reads[kReadCountWords - 1] = direct_reads_bounce().load(std::memory_order_relaxed);
 }
 
 int FileSource::open_file(uint32_t i) {
@@ -73,6 +79,7 @@ int FileSource::open_file(uint32_t i) {
     }
     if (x < 0) x = open(files_[i].path, O_RDONLY | O_CLOEXEC);
     KRK_CHECK(x >= 0, KRK_EIO, "open %s: %s", files_[i].path, strerror(errno));
+    if (direct_) rc_.add(is_direct_[i] ? &ReadCounts::direct_files : &ReadCounts::buffered_files, 1);
     fd_[i] = x;
     return KRK_OK;
 }
@@ -92,8 +99,8 @@ int FileSource::fill(const std::vector<FillTask>& tasks) {
         const auto& rt = pass ? odirect : plain;
         if (rt.empty()) continue;
         int e = 0;
-        long bad = pass == 1 && async_ && use_aio() ? aio_.read(rt, &e) : -2;
-        if (bad == -2) bad = par_read(rt, pass == 1, &e);
+        long bad = pass == 1 && async_ && use_aio() ? aio_.read(rt, &e, &rc_) : -2;
+        if (bad == -2) bad = par_read(rt, pass == 1, &e, &rc_);
         if (bad >= 0) {
             const char* path = files_[rt[bad].blob].path;
             if (e) set_error(KRK_EIO, "read blob: %s: %s", path, strerror(e));

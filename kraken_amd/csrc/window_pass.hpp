@@ -59,7 +59,9 @@ struct MemSource {
 
 // The cache files.  A blob's file is opened at its first chunk (O_DIRECT if wanted and the
 // file system has it) and closed after its last; live blobs <= the descriptor budget, so no
-// descriptor is reopened.
+// descriptor is reopened.  It counts which way its bytes came (ReadCounts, direct_read.hpp)
+// and leaves the counts as the calling thread's last (krk_windows_last_reads) when it goes.
+extern thread_local uint64_t t_last_reads[kReadCountWords];
 struct FileSource {
     static constexpr bool kMemory = false;
     // async: O_DIRECT chunks by Linux AIO and page-cache reads with readahead marks (the
@@ -76,6 +78,7 @@ struct FileSource {
     std::vector<char> is_direct_;
     std::unique_ptr<std::atomic<uint64_t>[]> ra_;  // each file's readahead mark (par_read)
     AioReader aio_;                                  // the O_DIRECT chunks of a window
+    ReadCounts rc_;
 };
 
 // File descriptors the file batches may hold open, shared by the whole process: a lease of

@@ -451,6 +451,12 @@ int krk_windows_last_direct(int* direct_windows) {
     return KRK_OK;
 }
 
+int krk_windows_last_reads(uint64_t* counts, int n) {
+    KRK_CHECK(counts && n >= 0, KRK_EINVAL, "windows_last_reads: null argument");
+    for (int k = 0; k < n; ++k) counts[k] = k < kReadCountWords ? t_last_reads[k] : 0;
+    return KRK_OK;
+}
+
 int krk_set_host_gather(int mode) {
     KRK_CHECK(mode >= -1 && mode <= 1, KRK_EINVAL, "host gather mode %d outside -1 (auto), 0, 1", mode);
     g_host_gather.store(mode);

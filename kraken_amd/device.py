@@ -644,6 +644,19 @@ def windows_last_call() -> dict:
             "resident_sample": round(ph[4].value, 4), "direct_reads": bool(dr.value)}
 
 
+READ_COUNTS = ("direct_files", "buffered_files", "window_bytes", "bounce_bytes", "bounce_preads", "cached_bytes",
+               "aio_reaped", "aio_rereads", "bounce_on")
+
+
+def windows_last_reads() -> dict:
+    """The calling thread's last file batch: which way its bytes came (krk_windows_last_reads)."""
+    v = (C.c_uint64 * len(READ_COUNTS))()
+    check(lib.krk_windows_last_reads(v, len(READ_COUNTS)))
+    out = dict(zip(READ_COUNTS, (int(x) for x in v)))
+    out["bounce_on"] = bool(out["bounce_on"])
+    return out
+
+
 def set_host_gather(mode: int):
     """krk_set_host_gather: -1 AUTO (default), 0 stage every window, 1 gather any size."""
     check(lib.krk_set_host_gather(int(mode)))

@@ -16,6 +16,7 @@ SHA-256 digest of uploader.verify / CAStore.WriteCacheFile (origin/blobserver/up
   blob equal to the oracle."""
 import hashlib
 import os
+import pathlib
 import resource
 
 import numpy as np
@@ -26,6 +27,22 @@ from kraken_amd._capi import KRK_EIO, KrakenError, check, krk_blob, lib
 from kraken_amd.windowed import c3_lengths
 
 pytestmark = pytest.mark.gpu
+
+@pytest.fixture
+def direct_path():
+    """A fresh directory where files open O_DIRECT (tests/window_matrix.py direct_dir: the build tree first; pytest's
+    tmp_path is often on a tmpfs, where FileSource falls back to buffered reads without a word)."""
+    from tests import window_matrix as M
+    with M.direct_tmp() as d:
+        if d is None:
+            pytest.skip(M.NO_DIRECT)
+        yield pathlib.Path(d)
+
+
+def _assert_read_direct(rd):
+    """krk_windows_last_reads of a direct batch: its files opened O_DIRECT, nothing through the page cache."""
+    assert rd["direct_files"] > 0 and rd["buffered_files"] == 0 and rd["cached_bytes"] == 0, rd
+
 
 EDGE = [0, 1, 63, 64, 65, 4095, 4096, 4097, (1 << 20) - 1, 1 << 20, (1 << 20) + 1, 3 * (1 << 20) + 5, 9_999_999]
 
@@ -39,7 +56,9 @@ def _write(tmp_path, name, data):
 
 @pytest.mark.parametrize("P", [1 << 20, 3, 4 << 20])
 @pytest.mark.parametrize("mode", ["gpu", "offload", "cap3", "direct_aio", "direct_sync"])
-def test_files_edge_lengths_match_oracle(gpu, orc, tmp_path, P, mode, monkeypatch):
+def test_files_edge_lengths_match_oracle(gpu, orc, tmp_path, request, P, mode, monkeypatch):
+    if mode.startswith("direct"):
+        tmp_path = request.getfixturevalue("direct_path")
     lens = EDGE if P != 3 else [0, 1, 2, 3, 4, 64, 65, 100_001]
     datas = [orc.synth(50 + i, L) for i, L in enumerate(lens)]
     paths = [_write(tmp_path, f"b{i}", d) for i, d in enumerate(datas)]
@@ -54,6 +73,7 @@ def test_files_edge_lengths_match_oracle(gpu, orc, tmp_path, P, mode, monkeypatc
     try:
         sums, dg = D.metainfo_digest_files(paths, lens, P)
         st = D.windows_last_call()
+        rd = D.windows_last_reads()
     finally:
         D.set_sha_host_offload(0)
         D.set_planner_rates(None)
@@ -66,14 +86,17 @@ def test_files_edge_lengths_match_oracle(gpu, orc, tmp_path, P, mode, monkeypatc
         assert st["max_live"] == 3 and st["windows"] >= len(lens) // 3
     if mode.startswith("direct"):
         assert st["direct_reads"], st
+        _assert_read_direct(rd)
+        assert rd["window_bytes"] + rd["bounce_bytes"] == sum(lens), rd
 
 
-def test_direct_batch_live_files_match_the_link(gpu, orc, tmp_path, monkeypatch):
+def test_direct_batch_live_files_match_the_link(gpu, orc, direct_path, monkeypatch):
     """Round 6: a batch read O_DIRECT keeps at most as many files live as it takes the windows'
     streams to outrun the host link (h2d / the eight-lane per-stream rate, rounded up to 64,
     at least 256) -- larger disk requests for cold batches.  With injected rates (30 GB/s,
     60 MB/s a stream) that is 512 of 1,300 files; KRK_LIVE_CAP still wins; every output equals
     hashlib / the oracle."""
+    tmp_path = direct_path
     rng = np.random.default_rng(77)
     lens = [int(x) for x in rng.integers(1, 40_000, 1300)]
     src = orc.synth(4242, max(lens))
@@ -84,11 +107,16 @@ def test_direct_batch_live_files_match_the_link(gpu, orc, tmp_path, monkeypatch)
         D.set_sha_host_offload(0)
         sums, dg = D.metainfo_digest_files(paths, lens, 1 << 14)
         st = D.windows_last_call()
+        rd = D.windows_last_reads()
         monkeypatch.setenv("KRK_LIVE_CAP", "700")
         sums2, dg2 = D.metainfo_digest_files(paths, lens, 1 << 14)
         st2 = D.windows_last_call()
+        rd2 = D.windows_last_reads()
     finally:
         D.set_planner_rates(None)
+    for x in (rd, rd2):
+        _assert_read_direct(x)
+        assert x["window_bytes"] + x["bounce_bytes"] == sum(lens), x
     assert st["direct_reads"] and st["max_live"] == 512, st
     assert st2["max_live"] == 700, st2
     for i in range(0, len(lens), 37):
@@ -141,8 +169,9 @@ def test_files_cold_batch_stays_on_windows_under_auto(gpu, orc, tmp_path):
 
 
 @pytest.mark.parametrize("mode", ["default", "direct_aio", "direct_sync"])
-def test_files_errors_keep_reference_texts(gpu, orc, tmp_path, mode, monkeypatch):
+def test_files_errors_keep_reference_texts(gpu, orc, tmp_path, request, mode, monkeypatch):
     if mode != "default":  # the same texts from the O_DIRECT reads (Linux AIO or preads)
+        tmp_path = request.getfixturevalue("direct_path")
         monkeypatch.setenv("KRK_FILE_DIRECT", "1")
         monkeypatch.setenv("KRK_FILE_AIO", "1" if mode == "direct_aio" else "0")
     d = orc.synth(1, 1 << 20)
@@ -163,6 +192,10 @@ def test_files_errors_keep_reference_texts(gpu, orc, tmp_path, mode, monkeypatch
     # the library is usable after the failures
     sums, dg = D.metainfo_digest_files([p], [1 << 20], 1 << 20)
     assert bytes(dg[0]) == hashlib.sha256(d.tobytes()).digest()
+    if mode != "default":
+        rd = D.windows_last_reads()
+        _assert_read_direct(rd)
+        assert rd["window_bytes"] + rd["bounce_bytes"] == 1 << 20, rd
 
 
 def test_files_host_offloaded_failure_reaches_caller(gpu, orc, tmp_path):

@@ -24,6 +24,19 @@ def _report(bad):
     assert bad == [], "\n".join(bad[:12])
 
 
+@pytest.fixture
+def direct_path():
+    """A fresh directory where files open O_DIRECT (M.direct_dir): the direct legs assert that they read that way."""
+    with M.direct_tmp() as d:
+        if d is None:
+            pytest.skip(M.NO_DIRECT)
+        yield d
+
+
+def _dir_for(leg, request, tmp_path):
+    return request.getfixturevalue("direct_path") if leg in M.DIRECT_LEGS else tmp_path
+
+
 C_CASES = {
     "A": M.case_a,                          # by the leg's alignment
     "A2-Pc5": lambda align: M.case_a2(),
@@ -36,13 +49,13 @@ C_CASES = {
 
 @pytest.mark.parametrize("leg", M.LEGS)
 @pytest.mark.parametrize("name", list(C_CASES))
-def test_group_c_every_way_up(gpu, tmp_path, monkeypatch, name, leg):
+def test_group_c_every_way_up(gpu, tmp_path, request, monkeypatch, name, leg):
     case = C_CASES[name](M.leg_align(leg))
     files_b = name == "B" and leg.startswith("files")
     # B's files: 17,084 of them (5 MB, a second or two to write; the leg runs however long the disk takes, a skip
     # by the clock made it come and go with the load of the machine); a process's descriptor budget may cap the
     # live files below KRK_LIVE_CAP
-    _report(M.run_leg(case, leg, tmp_path, monkeypatch.setenv, lower_cap_ok=files_b))
+    _report(M.run_leg(case, leg, _dir_for(leg, request, tmp_path), monkeypatch.setenv, lower_cap_ok=files_b))
 
 
 @pytest.mark.parametrize("ring", [2, 4])
@@ -59,8 +72,8 @@ def test_group_c_ring_depths(gpu, ring):
 
 @pytest.mark.parametrize("leg", ["staged", "arena0", "files", "files_aio", "files_sync"])
 @pytest.mark.parametrize("P", [M.MiB, 65_537])
-def test_group_d_windows_wide_enough_to_split(gpu, tmp_path, monkeypatch, P, leg):
-    _report(M.run_leg(M.case_d(P), leg, tmp_path, monkeypatch.setenv))
+def test_group_d_windows_wide_enough_to_split(gpu, tmp_path, request, monkeypatch, P, leg):
+    _report(M.run_leg(M.case_d(P), leg, _dir_for(leg, request, tmp_path), monkeypatch.setenv))
 
 
 @pytest.mark.parametrize("base", ["A2", "D"])
@@ -100,5 +113,6 @@ def test_group_f_piece_sums_host_pageable(gpu, monkeypatch):
 
 
 @pytest.mark.parametrize("direct", [False, True])
-def test_group_f_piece_sums_files(gpu, tmp_path, monkeypatch, direct):
-    _report(M.run_sums_files(M.case_f(4096), tmp_path, direct, monkeypatch.setenv))
+def test_group_f_piece_sums_files(gpu, tmp_path, request, monkeypatch, direct):
+    d = request.getfixturevalue("direct_path") if direct else tmp_path
+    _report(M.run_sums_files(M.case_f(4096), d, direct, monkeypatch.setenv))

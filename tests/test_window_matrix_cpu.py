@@ -280,3 +280,26 @@ def test_statistics_rule():
             "host_blobs": 0}
     assert M.stats_mismatches(wide, b, 64, True, wide_gather=True) == []
     assert M.stats_mismatches(dict(wide, gather_windows=0), b, 64, True, wide_gather=False) == []
+
+
+def test_group_r_cases_and_the_reads_checker():
+    """Group R: the cases' promises (300 tasks in each of the first two windows, two requests above the bounce buffer,
+    a first window that par_read splits), and reads_mismatches on counters that are right and wrong in each way."""
+    many, big = M.case_r_many(), M.case_r_big()
+    assert M.direct_tasks(many)[:2] == [300, 300] and M.direct_tasks(big) == [2]
+    first = sum((ln + 4095) // 4096 * 4096 for _, _, ln in M.case_d().replay(4096)[0][0])
+    assert first >= M.SPLIT_MIN
+    T = 1000
+    base = dict(direct_files=3, buffered_files=0, window_bytes=0, bounce_bytes=0, bounce_preads=0, cached_bytes=0,
+                aio_reaped=0, aio_rereads=0, bounce_on=False)
+    zero_copy = dict(base, window_bytes=T)
+    bounced = dict(base, bounce_bytes=T, bounce_preads=2, bounce_on=True)
+    flipped = dict(base, window_bytes=400, bounce_bytes=600, bounce_preads=1, bounce_on=True)
+    assert M.reads_mismatches(zero_copy, T) == [] and M.reads_mismatches(bounced, T) == []
+    assert M.reads_mismatches(bounced, T, 1) == [] and M.reads_mismatches(flipped, T, 5) == []
+    assert M.reads_mismatches(flipped, T) == []
+    for rd, refused in ((dict(zero_copy, direct_files=0), None), (dict(zero_copy, buffered_files=1), None),
+                        (dict(base, cached_bytes=T), None), (dict(zero_copy, window_bytes=T - 1), None),
+                        (dict(zero_copy, bounce_preads=1), None), (zero_copy, 1), (flipped, 1), (bounced, 5),
+                        (dict(bounced, bounce_on=False), 1), (dict(bounced, bounce_preads=0), 1)):
+        assert M.reads_mismatches(rd, T, refused), (rd, refused)

@@ -26,14 +26,23 @@ Groups (W = 1 MiB unless said; c(k, align) = (W // k) // align * align):
   E   layout and mixing: permuted and gapped sums offsets from 1,000, n = 1, empty blobs only, a host-offload subset
   F   the CRC-only packers, lengths built against pack_replay, three GPU shares
 
+  R   which way a file batch's bytes came (krk_windows_last_reads): the direct legs assert that their files were opened
+      O_DIRECT and nothing came through the page cache, and the *_refused legs run them in child processes under the
+      diag library's KRK_DIRECT_REFUSE=N, where the N-th O_DIRECT read aimed at a window and every later one is
+      refused as on a machine whose pinned windows take no disk DMA (direct_read.hpp): `python -m tests.window_matrix
+      reads SCENARIO DIR`, driven by tests/test_gpu_file_reads.py
+
 Importing this module loads no library; the runners import kraken_amd._capi when called."""
+import contextlib
 import ctypes as C
 import functools
 import hashlib
 import json
 import os
+import shutil
 import sys
 import tempfile
+import threading
 import time
 import zlib
 from dataclasses import dataclass
@@ -693,8 +702,9 @@ def last_call():
 
 
 def stats_mismatches(st, case, align, page_locked, registered=False, wide_gather=None, direct_reads=None, blobs=None,
-                     host_blobs=0):
-    """krk_windows_last_* against the replay of the blobs the call put through the windows."""
+                     host_blobs=0, reads=None, refused=None):
+    """krk_windows_last_* against the replay of the blobs the call put through the windows.  reads: the direct legs'
+    krk_windows_last_reads, which must say that the bytes were read O_DIRECT (reads_mismatches)."""
     windows, max_live = case.replay(align, blobs)
     narrow = sum(1 for w in windows if len(w) <= DIRECT_MAX)
     bad = []
@@ -713,6 +723,8 @@ def stats_mismatches(st, case, align, page_locked, registered=False, wide_gather
         bad.append("direct_reads %s, want %s" % (st["direct_reads"], direct_reads))
     if st["host_blobs"] != host_blobs:
         bad.append("host_blobs %d, want %d" % (st["host_blobs"], host_blobs))
+    if reads is not None:
+        bad += reads_mismatches(reads, sum(case.lens), refused)
     return [case.name + ": " + b + " (" + json.dumps({k: st[k] for k in (
         "windows", "max_live", "direct_windows", "gather_windows", "direct_reads", "host_blobs")}) + ")" for b in bad]
 
@@ -721,16 +733,126 @@ def stats_mismatches(st, case, align, page_locked, registered=False, wide_gather
 LEGS = ("staged", "registered", "arena0", "arena1", "arena8", "arena15", "arena1_nogather", "files", "files_aio",
         "files_sync")
 DIRECT_LEGS = ("files_aio", "files_sync")
+# the direct legs with the windows refusing the reads (KRK_DIRECT_REFUSE, diag library): in child processes only, the
+# switch to the bounce buffer is process-wide and permanent
+REFUSED_LEGS = ("files_aio_refused", "files_sync_refused")
 
 
 def leg_align(leg):
     """The schedule's alignment on a leg: 4 KiB chunks for O_DIRECT reads, SHA-256 blocks otherwise."""
-    return 4096 if leg in DIRECT_LEGS else 64
+    return 4096 if leg in DIRECT_LEGS + REFUSED_LEGS else 64
 
 
-def run_leg(case, leg, directory, setenv, ring=RING, lower_cap_ok=False):
+# ------------------------------------------------------------------------------ group R: which way the bytes came
+@functools.lru_cache(maxsize=None)
+def direct_dir():
+    """A directory whose filesystem opens files O_DIRECT (a tmpfs does not, and FileSource then reads buffered without
+    a word): the repository's build tree first, then the temporary directories.  None where there is none."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    for d in (os.path.join(root, "build", "direct_files"), tempfile.gettempdir(), "/var/tmp"):
+        try:
+            os.makedirs(d, exist_ok=True)
+            fd, p = tempfile.mkstemp(dir=d)
+        except OSError:
+            continue
+        try:
+            os.write(fd, b"\0" * 4096)
+            os.close(fd)
+            os.close(os.open(p, os.O_RDONLY | os.O_DIRECT))
+            return d
+        except OSError:
+            continue
+        finally:
+            os.unlink(p)
+    return None
+
+
+NO_DIRECT = "no filesystem here accepts O_DIRECT"
+
+
+@contextlib.contextmanager
+def direct_tmp():
+    """A fresh directory under direct_dir(), removed afterwards; None where no filesystem accepts O_DIRECT."""
+    base = direct_dir()
+    if base is None:
+        yield None
+        return
+    d = tempfile.mkdtemp(dir=base)
+    try:
+        yield d
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+
+
+def last_reads():
+    from kraken_amd import device as D
+    return D.windows_last_reads()
+
+
+def machine_refuses(directory):
+    """Whether page-locked memory of this machine refuses an O_DIRECT read, asked without the library's read path:
+    one os.preadv of a 4 KiB file into a hipHostMalloc page (a krk_host_alloc block below 2 MiB is one, as the staging
+    windows are: runtime.cpp krk_host_alloc says so and names this probe).  EFAULT is the refusal; any other error is
+    raised."""
+    import errno
+    from kraken_amd._capi import check, lib
+    p = C.c_void_p()
+    check(lib.krk_host_alloc(8192, C.byref(p)))
+    path = os.path.join(str(directory), "probe")
+    try:
+        with open(path, "wb") as f:
+            f.write(b"\x5a" * 4096)
+        page = (C.c_char * 4096).from_address((p.value + 4095) & ~4095)
+        fd = os.open(path, os.O_RDONLY | os.O_DIRECT)
+        try:
+            return os.preadv(fd, [page], 0) != 4096
+        except OSError as e:
+            if e.errno != errno.EFAULT:
+                raise
+            return True
+        finally:
+            os.close(fd)
+    finally:
+        os.unlink(path)
+        lib.krk_host_free(p)
+
+
+def reads_mismatches(rd, total, refused=None):
+    """krk_windows_last_reads of a direct batch of `total` bytes that succeeded: every file opened O_DIRECT, nothing
+    through the page cache, every byte counted once.  refused: None = whatever this machine's windows do (the switch
+    says which), 1 = every read refused (all bytes bounced), N > 1 = the switch flipped in mid-batch."""
+    bad = []
+    if not rd["direct_files"] or rd["buffered_files"] or rd["cached_bytes"]:
+        bad.append("not read O_DIRECT: %d files direct, %d buffered, %d bytes through the page cache" %
+                   (rd["direct_files"], rd["buffered_files"], rd["cached_bytes"]))
+    if rd["window_bytes"] + rd["bounce_bytes"] + rd["cached_bytes"] != total:
+        bad.append("window + bounce + page-cache bytes do not add up to %d" % total)
+    if refused is not None and not rd["bounce_on"]:
+        bad.append("the bounce switch is off after a refusal")
+    if refused == 1 or (refused is None and rd["bounce_on"] and not rd["window_bytes"]):
+        if rd["window_bytes"] or rd["bounce_bytes"] != total:
+            bad.append("every read refused, yet not every byte bounced")
+        if total and rd["bounce_preads"] < 1:
+            bad.append("bytes bounced without a bounce pread")
+    elif refused is not None:
+        if not (rd["window_bytes"] and rd["bounce_bytes"]):
+            bad.append("the switch flipped in mid-batch, yet one of window / bounce bytes is 0")
+    elif not rd["bounce_on"]:
+        if rd["bounce_bytes"] or rd["bounce_preads"] or rd["window_bytes"] != total:
+            bad.append("the switch is off, yet not every byte went straight into a window")
+    return [b + " (" + json.dumps(rd) + ")" for b in bad]
+
+
+def direct_tasks(case, align=4096):
+    """The read tasks of each window of a direct batch: its chunks of at least one byte."""
+    return [sum(1 for _, _, ln in w if ln) for w in case.replay(align)[0]]
+
+
+def run_leg(case, leg, directory, setenv, ring=RING, lower_cap_ok=False, refused=None):
     """`case` through one way up: every entry point of that way, whole-array comparison and the call statistics.
     setenv(name, value) sets the environment for the calls (read per call).  Returns the mismatches.
+    The direct legs' files must lie where O_DIRECT opens (direct_tmp); a *_refused leg runs in a process that loaded
+    the diag library with KRK_DIRECT_REFUSE=`refused`.
     lower_cap_ok: a file batch may run under a lower live cap than KRK_LIVE_CAP (the descriptor lease caps it by the
     process's descriptor budget); the replay then takes the cap the call reports."""
     from kraken_amd._capi import check, lib
@@ -741,16 +863,18 @@ def run_leg(case, leg, directory, setenv, ring=RING, lower_cap_ok=False):
     windows = case.replay(align)[0]
     if leg.startswith("files"):
         setenv("KRK_FILE_DIRECT", "0" if leg == "files" else "1")
-        setenv("KRK_FILE_AIO", "0" if leg == "files_sync" else "1")
+        setenv("KRK_FILE_AIO", "0" if leg.startswith("files_sync") else "1")
+        assert (leg in REFUSED_LEGS) == (refused is not None), (leg, refused)
         src = FileSource(case, directory)
         out = call("metainfo_digest_files", case, src)
         st = last_call()
+        rd = last_reads() if leg != "files" else None
         if lower_cap_ok and st["max_live"] < min(case.cap, case.n):
             assert st["max_live"] >= 16, st
             case = Case(case.name, case.lens, case.plens, case.soff, case.window_mb, st["max_live"], case.seed)
             windows = case.replay(align)[0]
         bad += mismatches(out, "zero", windows, place, ring)
-        bad += stats_mismatches(st, case, align, False, direct_reads=leg != "files")
+        bad += stats_mismatches(st, case, align, False, direct_reads=leg != "files", reads=rd, refused=refused)
         return [leg + ": " + b for b in bad]
     arena = leg.startswith("arena")
     misalign = int(leg[5:].split("_")[0]) if arena else 0
@@ -793,13 +917,16 @@ def run_sums_host(case, fraction, arena, setenv, misalign=1):
     return bad
 
 
-def run_sums_files(case, directory, direct, setenv):
-    """krk_piece_sums_files at W = 1 MiB on the session's placement (KRK_PLACE_GPU)."""
+def run_sums_files(case, directory, direct, setenv, refused=None):
+    """krk_piece_sums_files at W = 1 MiB on the session's placement (KRK_PLACE_GPU).  direct: the files lie where
+    O_DIRECT opens, and the reads must say so; refused: as run_leg's."""
     from kraken_amd import device as D
     setenv("KRK_WINDOW_MB", "1")
     setenv("KRK_FILE_DIRECT", "1" if direct else "0")
     out = call("piece_sums_files", case, FileSource(case, directory))
     bad = mismatches(out, GAPS["piece_sums_files"], pack_replay(case.lens, W1, 4096), 4096)
+    if direct:
+        bad += [case.name + ": " + b for b in reads_mismatches(last_reads(), sum(case.lens), refused)]
     if sum(case.lens) and D.crc_host_split()[:2] != (sum(case.lens), 0):
         bad.append("%s: krk_crc_host_split %r, want every byte on the GPU" % (case.name, D.crc_host_split()[:2]))
     return bad
@@ -856,9 +983,190 @@ def run_mixed(case, directory, setenv):
     return bad
 
 
+# ------------------------------------------------------------------------------ group R: the scenarios of a child
+R_FILES, R_LIVE = 300, 300
+
+
+@functools.lru_cache(maxsize=None)
+def case_r_many(seed=110, n=R_FILES):
+    """300 live files of 4,097 .. 20,000 bytes: at 4 KiB a chunk the first window holds 300 read tasks, more than the
+    AIO reader keeps in flight (AioReader::kAioDepth = 256), and every file has a chunk in the second window too."""
+    lens = [int(x) for x in np.random.default_rng(seed).integers(4097, 20_001, n)]
+    case = _case("R/many%d" % seed, lens, [5000] * n, 1, n, seed, 4096)
+    tasks = direct_tasks(case)
+    assert tasks[0] == n and (n <= 256 or (tasks[1] == n and len(tasks) >= 3)), tasks
+    return case
+
+
+def case_r_big():
+    """Two requests larger than the 1 MiB bounce buffer in one 8 MiB window: 3 MiB + 5 and 2 MiB, KRK_LIVE_CAP=2."""
+    case = _case("R/big", [3 * MiB + 5, 2 * MiB], [MiB, MiB], 8, 2, 111, 4096)
+    assert direct_tasks(case) == [2]
+    return case
+
+
+def _edge_scenario(directory, refused, P):
+    """The EDGE lengths of tests/test_gpu_files.py at piece length P, against hashlib and the oracle.  One piece length
+    a process: the first direct call of a process is the only one the AIO reader sees refused (the switch is for good)."""
+    from kraken_amd import device as D
+    from oracle import oracle as O
+    from tests.test_gpu_files import EDGE
+    bad = []
+    datas = [O.synth(50 + i, L) for i, L in enumerate(EDGE)]
+    paths = []
+    for i, d in enumerate(datas):
+        paths.append(os.path.join(directory, "e%d" % i))
+        with open(paths[-1], "wb") as f:
+            f.write(memoryview(d))
+    sums, dg = D.metainfo_digest_files(paths, EDGE, P)
+    rd = D.windows_last_reads()
+    for i, d in enumerate(datas):
+        if bytes(dg[i]) != hashlib.sha256(memoryview(d)).digest():
+            bad.append("P=%d: digest of file %d (L=%d) differs" % (P, i, EDGE[i]))
+        if not np.array_equal(sums[i], O.calc_piece_sums(d, P)[1]):
+            bad.append("P=%d: piece sums of file %d (L=%d) differ" % (P, i, EDGE[i]))
+    if not D.windows_last_call()["direct_reads"]:
+        bad.append("P=%d: direct_reads is off" % P)
+    bad += ["P=%d: %s" % (P, b) for b in reads_mismatches(rd, sum(EDGE), refused)]
+    return bad, {"reads": rd, "total": sum(EDGE), "tasks": sum(1 for L in EDGE if L)}
+
+
+# name: (declared, actual, KRK_WINDOW_MB)
+SHORT = {"one_byte": (100_000, 99_999, 1), "4k_edge": (100_000, 98_304, 1), "1m_of_3m": (3 * MiB, MiB, 4),
+         "1m_of_3m_w1": (3 * MiB, MiB, 1)}
+
+
+def _short_scenario(directory, refused, name):
+    """A file shorter than declared -- by one byte, to a 4 KiB edge, to exactly 1 MiB inside a 3 MiB request (a 4 MiB
+    window) or at the end of a 1 MiB request (a 1 MiB window) -- as the FIRST direct call of its process, so that on
+    the AIO leg it is the reaper's re-read of the refused request that meets the end of the file; the reference's text.
+    Then the same file at its true length.  name "missing": a missing file, of bytes and empty."""
+    from kraken_amd import device as D
+    from kraken_amd._capi import KRK_EIO, KrakenError
+    bad = []
+    data = np.frombuffer(np.random.default_rng(112).bytes(3 * MiB), dtype=np.uint8)
+    if name == "missing":
+        p, missing = os.path.join(directory, "here"), os.path.join(directory, "nope")
+        with open(p, "wb") as f:
+            f.write(memoryview(data[:MiB]))
+        for L in (5, 0):
+            try:
+                D.metainfo_digest_files([p, missing], [MiB, L], MiB)
+                bad.append("missing file of %d bytes: no error" % L)
+            except KrakenError as e:
+                if e.code != KRK_EIO or ("open %s: No such file or directory" % missing) not in str(e):
+                    bad.append("missing file of %d bytes: code %d, text %r" % (L, e.code, str(e)))
+        declared = actual = MiB
+    else:
+        declared, actual, window_mb = SHORT[name]
+        os.environ["KRK_WINDOW_MB"] = str(window_mb)
+        p = os.path.join(directory, "short")
+        with open(p, "wb") as f:
+            f.write(memoryview(data[:actual]))
+        try:
+            D.metainfo_digest_files([p], [declared], MiB)
+            bad.append("%s: no error" % name)
+        except KrakenError as e:
+            if e.code != KRK_EIO or not str(e).endswith("read blob: %s: unexpected EOF" % p):
+                bad.append("%s: code %d, text %r" % (name, e.code, str(e)))
+        failed = D.windows_last_reads()
+        if os.environ.get("KRK_FILE_AIO") == "1" and (failed["aio_reaped"], failed["aio_rereads"]) != (1, 1):
+            bad.append("%s: the failing call reaped %d AIO requests and re-read %d, not one" %
+                       (name, failed["aio_reaped"], failed["aio_rereads"]))
+    # the library is usable after the failure: the file at its true length
+    _, dg = D.metainfo_digest_files([p], [actual], MiB)
+    if bytes(dg[0]) != hashlib.sha256(memoryview(data[:actual])).digest():
+        bad.append("%s: wrong digest at the true length" % name)
+    rd = D.windows_last_reads()
+    bad += ["%s: %s" % (name, b) for b in reads_mismatches(rd, actual, refused)]
+    return bad, {"reads": rd}
+
+
+def _threads_scenario(directory):
+    """Two threads of this process, each with a direct batch of 40 files at the same time.  Which thread's read is the
+    third of the process the scheduler decides, so the counters are held to the byte accounting only."""
+    cases = [case_r_many(113 + t, 40) for t in range(2)]
+    out, errors = [None, None], []
+    os.environ.update(KRK_WINDOW_MB="1", KRK_LIVE_CAP="40", KRK_FILE_DIRECT="1", KRK_FILE_AIO="1")
+    srcs = []
+    for t, case in enumerate(cases):
+        d = os.path.join(directory, "t%d" % t)
+        os.mkdir(d)
+        srcs.append(FileSource(case, d))
+    gate = threading.Barrier(2)
+
+    def work(t):
+        try:
+            gate.wait(timeout=30)
+            o = call("metainfo_digest_files", cases[t], srcs[t])
+            out[t] = (o, last_call(), last_reads())  # the thread's own last call
+        except Exception as e:  # noqa: BLE001 -- reported below
+            errors.append("thread %d: %r" % (t, e))
+
+    th = [threading.Thread(target=work, args=(t,)) for t in range(2)]
+    for x in th:
+        x.start()
+    for x in th:
+        x.join(timeout=60)
+    bad = errors + ["thread %d did not finish" % t for t, x in enumerate(th) if x.is_alive()]
+    if bad:
+        return bad, {}
+    for t, (o, st, rd) in enumerate(out):
+        bad += ["thread %d: %s" % (t, b) for b in mismatches(o, "zero", cases[t].replay(4096)[0], 4096)]
+        bad += ["thread %d: %s" % (t, b) for b in stats_mismatches(st, cases[t], 4096, False, direct_reads=True)]
+        # the third read of the process flips the switch: which thread's it is, the scheduler decides
+        bad += ["thread %d: %s" % (t, b) for b in reads_mismatches(rd, sum(cases[t].lens), None)]
+    return bad, {"reads": [o[2] for o in out]}
+
+
+def reads_main(argv):
+    """python -m tests.window_matrix reads SCENARIO DIR: one scenario of group R in this process, whose library and
+    KRK_DIRECT_REFUSE the parent chose (the diag library reads it; unset: the control).  One JSON line; exit status 1
+    on a mismatch."""
+    scenario, directory = argv
+    from kraken_amd import _capi
+    from kraken_amd import device as D
+    D.set_device(0)
+    _capi.check(_capi.lib.krk_set_sha_host_offload(0))
+    _capi.check(_capi.lib.krk_set_crc_placement(_capi.KRK_PLACE_GPU))
+    refused = asked = int(os.environ["KRK_DIRECT_REFUSE"]) if os.environ.get("KRK_DIRECT_REFUSE") else None
+    suffix = "_refused" if refused else ""
+    # Windows that refuse the reads for real refuse the first one, whatever N says: the counters are then those of
+    # N = 1, and no read can go straight into a window (the control, refused None, reads the switch instead).
+    real = machine_refuses(directory)
+    if real and refused:
+        refused = 1
+    setenv = os.environ.__setitem__
+    t0, extra = time.perf_counter(), {}
+    if scenario.startswith("edge:"):
+        bad, extra = _edge_scenario(directory, refused, int(scenario[5:]))
+    elif scenario.startswith("short:"):
+        bad, extra = _short_scenario(directory, refused, scenario[6:])
+    elif scenario == "threads":
+        bad, extra = _threads_scenario(directory)
+    elif scenario == "sums":
+        bad = run_sums_files(case_f(4096), directory, True, setenv, refused)
+        extra = {"reads": last_reads(), "total": sum(case_f(4096).lens)}
+    else:
+        leg, name = scenario.split(":")  # files_aio:many, files_sync:big, files_sync:split ...
+        case = {"many": case_r_many, "big": case_r_big, "split": case_d}[name]()
+        bad = run_leg(case, leg + suffix, directory, setenv, refused=refused)
+        extra = {"reads": last_reads(), "tasks": direct_tasks(case), "total": sum(case.lens)}
+    reads = extra.get("reads") or D.windows_last_reads()  # of the threads that made the calls
+    for rd in reads if isinstance(reads, list) else [reads]:
+        if rd["bounce_on"] != bool(real or asked):
+            bad.append("the bounce switch is %s; this machine's windows %s O_DIRECT reads and KRK_DIRECT_REFUSE is %s"
+                       % (rd["bounce_on"], "refuse" if real else "accept", asked))
+    print(json.dumps(dict(extra, scenario=scenario, refused=asked, machine_refuses=real, seconds=round(time.perf_counter() - t0, 3),
+                          n_mismatches=len(bad), mismatches=bad[:8])), flush=True)
+    return 1 if bad else 0
+
+
 def main(argv):
     """python -m tests.window_matrix LEG [LEG ...]: group A through the legs in this process (the ring depth is
     fixed per process: KRK_STAGING_WINDOWS), one JSON line a leg; exit status 1 on a mismatch."""
+    if argv and argv[0] == "reads":
+        return reads_main(argv[1:])
     from kraken_amd import device as D
     from kraken_amd._capi import check, lib
     D.set_device(0)
