@@ -357,6 +357,101 @@ int krk_piece_resend_round_dev(const krk_request_torrent* torrents_host, const k
                                const krk_failed_request* failed_host, uint32_t* target_out,
                                int32_t* quota_left_out, uint32_t* n_resent_out, void* stream);
 
+/* ------------------------------------------- request table rounds
+ * The piece request table of every torrent of a batch, kept beside the rows of a request round:
+ * piecerequest.Manager's `requests` and `requestsByPeer`, expiry, requestQuota, validRequest,
+ * GetFailedRequests, Clear, ClearPeer and Mark* (piecerequest/manager.go).  A torrent is its
+ * krk_request_torrent, unchanged (KRK_PR_ALLOW_DUPLICATES is the one flag read; the policy bits,
+ * the seed and piece_off are not), and a table of up to `cap` entries (cap <= KRK_RT_MAX_ENTRIES)
+ * at entries[entry_off ..], compact and in recording order, n_entries[t] of them in use: table
+ * order restricted to one piece is the order of requests[piece].  status is 0 (pending) or
+ * KRK_PR_EXPIRED / KRK_PR_UNSENT / KRK_PR_INVALID; peer is an index < n_peers.  One round, at the
+ * clock `now` with the request `timeout` and the pipeline `limit`, runs a torrent's lists in this
+ * order:
+ *   1 arrived  pieces, strictly ascending: the bit is set in have, every entry of the piece is
+ *              dropped (Manager.Clear).
+ *   2 gone     peers, strictly ascending: every entry of the peer is dropped, its bits_p row zeroed.
+ *   3 marks    krk_failed_request with status KRK_PR_UNSENT or KRK_PR_INVALID: every entry with
+ *              that (piece, peer) takes the status (MarkUnsent / MarkInvalid); of two marks that
+ *              hit one entry the later one stays.
+ *   4 holds    krk_request_pair, strictly ascending by (peer, piece): bit piece of bits_p is set
+ *              (handleAnnouncePiece, dispatch/dispatcher.go:488-496).
+ *   5 records  appended as pending with sent_at = now: the explicit krk_request_pair list in
+ *              order (the targets of a resend round), then, when picks and n_picked are given, for
+ *              p = 0 .. P-1 and j < min(n_picked[peer_off + p], limit) the pair
+ *              (picks[(peer_off + p) * limit + j], p) -- krk_piece_request_round_dev's output, read
+ *              where it lies.  An entry past cap, or a pick >= n_pieces, is dropped and counted in
+ *              n_dropped_out[t].
+ *   6 derive   live(e) = pending && !(now > sent_at + timeout):
+ *              quota_out[peer_off + p] = max(limit - #live entries of p, 0)       (requestQuota)
+ *              bit i of blocked_p = a live entry (i, p) under KRK_PR_ALLOW_DUPLICATES, a live
+ *              entry for i to anybody without it (validRequest); every word of every blocked row
+ *              is stored, tail bits clear.
+ *              failed_out[entry_off ..] (nullable, with n_failed_out) = every entry that is not
+ *              live, a pending one as KRK_PR_EXPIRED, ascending by piece and in table order inside
+ *              a piece; n_failed_out[t] its length.  It is the list krk_piece_resend_round* takes.
+ *              Failed entries stay in the table, as GetFailedRequests leaves them.
+ * One deliberate difference from the reference: ClearPeer ejects only the first entry a piece
+ * (manager.go:188-196) and leaves the rest to block their pieces under a PeerID that no longer
+ * connects; `gone` drops every entry of the peer.  An entry no valid round wrote (piece >=
+ * n_pieces, peer >= n_peers, status > 3) is dropped with the removed.
+ *
+ * bits, entries and n_entries are read and written; every quota_out, blocked word, n_dropped_out
+ * and (when asked for) failed_out / n_failed_out element a torrent owns is stored by the call.
+ * KRK_EINVAL, refused before anything is touched: a list that does not ascend as required, a
+ * piece >= n_pieces or a peer >= n_peers in a host list, a status outside its set, cap above the
+ * maximum, a non-zero reserved field, now < 0, timeout < 0 or their sum past INT64_MAX, a limit
+ * outside [1, KRK_PR_MAX_LIMIT], an unknown flag bit, a list of 2^32 entries or more, a NULL that
+ * is not nullable (picks with n_picked and failed_out with n_failed_out are nullable together).
+ * The regions the torrents name in one array must not overlap. */
+#define KRK_RT_MAX_ENTRIES 4096u
+typedef struct {
+    uint32_t piece;
+    uint32_t peer;     /* index among the torrent's peers */
+    uint32_t status;   /* 0 pending, KRK_PR_EXPIRED, KRK_PR_UNSENT, KRK_PR_INVALID */
+    uint32_t reserved; /* 0 */
+    int64_t sent_at;
+} krk_request_entry;
+typedef struct {
+    uint32_t piece;
+    uint32_t peer;
+} krk_request_pair;
+typedef struct {
+    uint64_t entry_off;  /* first entry in entries and in failed_out */
+    uint32_t cap;        /* <= KRK_RT_MAX_ENTRIES */
+    uint32_t reserved;   /* 0 */
+    uint64_t arrived_off, n_arrived; /* in arrived (pieces) */
+    uint64_t gone_off, n_gone;       /* in gone (peers) */
+    uint64_t mark_off, n_marks;      /* in marks */
+    uint64_t hold_off, n_holds;      /* in holds */
+    uint64_t record_off, n_records;  /* in records */
+} krk_table_torrent;     /* parallel to torrents[] */
+/* The whole round of n_torrents torrents on the host.  Also KRK_EINVAL: n_entries[t] > cap.  No
+ * device. */
+int krk_request_table_round(const krk_request_torrent* torrents, const krk_table_torrent* tables, uint64_t n_torrents,
+                            uint64_t* bits, krk_request_entry* entries, uint32_t* n_entries, const uint32_t* arrived,
+                            const uint32_t* gone, const krk_failed_request* marks, const krk_request_pair* holds,
+                            const krk_request_pair* records, const uint32_t* picks, const uint32_t* n_picked,
+                            int64_t now, int64_t timeout, uint32_t limit, int32_t* quota_out,
+                            krk_failed_request* failed_out, uint32_t* n_failed_out, uint32_t* n_dropped_out);
+/* The same on the device (request_table.hip), bit for bit; asynchronous on `stream`: one launch,
+ * one workgroup a torrent.  bits_dev, entries_dev, n_entries_dev, picks_dev, n_picked_dev and the
+ * outputs are device memory or page-locked host memory (krk_host_alloc), bits_dev and entries_dev
+ * 8-byte and the others 4-byte aligned: anything else is KRK_EINVAL before anything is launched.
+ * torrents_host, tables_host and the five lists are host memory: the lists are checked as above,
+ * and all of them are copied into the library's staging, before the call returns.  The device
+ * form cannot read n_entries_dev before the launch and reads a count above cap as cap.
+ * n_torrents == 0 is KRK_OK; KRK_ENODEV without a gfx950 device: there is no fall-back to the
+ * host form. */
+int krk_request_table_round_dev(const krk_request_torrent* torrents_host, const krk_table_torrent* tables_host,
+                                uint64_t n_torrents, uint64_t* bits_dev, krk_request_entry* entries_dev,
+                                uint32_t* n_entries_dev, const uint32_t* arrived_host, const uint32_t* gone_host,
+                                const krk_failed_request* marks_host, const krk_request_pair* holds_host,
+                                const krk_request_pair* records_host, const uint32_t* picks_dev,
+                                const uint32_t* n_picked_dev, int64_t now, int64_t timeout, uint32_t limit,
+                                int32_t* quota_out, krk_failed_request* failed_out, uint32_t* n_failed_out,
+                                uint32_t* n_dropped_out, void* stream);
+
 /* ------------------------------------------- announce rounds
  * Whom an announcing peer talks to: the tracker's announce (tracker/trackerserver/announce.go:75-115)
  * for a batch of announces at one clock instant -- peerstore UpdatePeer and GetPeers

@@ -267,6 +267,11 @@ int krk_piece_request_geometry(uint64_t* pieces_per_pass, uint64_t* thread_strid
  * further passes, whose state is in memory and not in registers) -- for the tests that pin
  * krk_piece_resend_round_dev's edges.  No device. */
 int krk_piece_resend_geometry(uint64_t* peers_per_pass);
+/* The shape of request_table.hip as built (kernel name "request_table"): the entries one step of
+ * the in-place compaction takes (one a thread; the record and failed-list ranks go in steps of
+ * the same size) and the keys one workgroup sorts in LDS (the most entries a table holds) -- for
+ * the tests that pin krk_request_table_round_dev's edges.  No device. */
+int krk_request_table_geometry(uint64_t* chunk, uint64_t* tile);
 /* The shape of the SHA-256 host share as built (offload.cpp): the bytes of one device-to-host copy
  * (a chain longer than that comes down in several), the pinned buffers an offload thread's copy
  * ring has (a chain of more chunks than that wraps it) and those of a resumer

@@ -413,6 +413,41 @@ hipError_t launch_piece_resend(const RsTorrent* tors, uint64_t n_tors, const uin
                                const rs::Failed* failed, int32_t* left, uint32_t* mark, uint32_t* target,
                                uint32_t* n_resent, hipStream_t s);
 
+// One torrent of a request table round (request_table.hip, request_table_math.hpp): its rows as a
+// request round's, its table entries[entry_off, + cap) with the count at n_entries[index], its
+// failed list at failed[entry_off ..], its quotas at quota[peer_off ..] and its picks rows of
+// `limit` from peer_off * limit.  Its five staged lists start at arrived_at / gone_at (uint32),
+// mark_at (rs::Failed), hold_at / record_at (rt::Pair), elements of their own arrays.
+namespace rt {
+struct Entry;
+struct Pair;
+struct Round;
+}
+struct alignas(16) RtTorrent {
+    uint64_t n_pieces;  // < 2^32
+    uint64_t bits_off;
+    uint64_t peer_off;
+    uint64_t entry_off;
+    uint64_t arrived_at, gone_at, mark_at, hold_at, record_at;
+    uint32_t n_arrived, n_gone, n_marks, n_holds, n_records;
+    uint32_t n_peers;
+    uint32_t flags;  // pr::kAllowDuplicates is read
+    uint32_t cap;    // <= kRtMaxEntries
+    uint64_t pad;
+};
+static_assert(sizeof(RtTorrent) == 112, "RtTorrent layout");
+constexpr uint32_t kRtMaxEntries = 4096;  // KRK_RT_MAX_ENTRIES: a table's keys fit the workgroup's LDS
+constexpr uint32_t kRtChunk = 256;        // the entries one step of the compaction takes: one a thread
+constexpr uint32_t kRtTile = kRtMaxEntries;  // the keys one workgroup sorts in LDS
+// One workgroup a torrent runs the round's six steps in order: bits, entries and n_entries are
+// read and written, every quota, blocked word, n_dropped and (failed nullable) failed / n_failed
+// entry stored.  picks / n_picked nullable together.  The lists are valid (rt::lists_error).
+hipError_t launch_request_table(const RtTorrent* tors, uint64_t n_tors, const uint32_t* arrived, const uint32_t* gone,
+                                const rs::Failed* marks, const rt::Pair* holds, const rt::Pair* records,
+                                const uint32_t* picks, const uint32_t* n_picked, const rt::Round& round, uint64_t* bits,
+                                rt::Entry* entries, uint32_t* n_entries, int32_t* quota, rs::Failed* failed,
+                                uint32_t* n_failed, uint32_t* n_dropped, hipStream_t s);
+
 // ---------------------------------------------------------------- announce rounds
 // One announce round (announce_round.hip, announce_math.hpp): the update launch sets every
 // announcer's bits in window 0 of its torrent (atomic or), the handout launch -- one wave an

@@ -8,7 +8,7 @@ import os
 import numpy as np
 
 from ._capi import (check, krk_blob, krk_file_blob, krk_chunk, krk_launch_rec, krk_nodes, krk_planner_rates,
-                    krk_request_torrent, krk_resend_torrent, krk_failed_request, krk_announce_torrent, krk_announce, krk_conn_torrent,
+                    krk_request_torrent, krk_resend_torrent, krk_failed_request, krk_table_torrent, krk_announce_torrent, krk_announce, krk_conn_torrent,
                     krk_conn_lists, krk_conn_transition, krk_conn_incoming, lib)
 
 ALIGN = 256  # every blob starts 256-byte aligned in the arena
@@ -1039,6 +1039,144 @@ def piece_resend_geometry() -> int:
     s = C.c_uint64()
     check(lib.krk_piece_resend_geometry(C.byref(s)))
     return int(s.value)
+
+
+# ------------------------------------------------------------------ request table rounds
+RT_MAX_ENTRIES = 4096
+RT_ENTRY = np.dtype([("piece", "<u4"), ("peer", "<u4"), ("status", "<u4"), ("reserved", "<u4"), ("sent_at", "<i8")])
+RT_FAILED = np.dtype([("piece", "<u4"), ("peer", "<u4"), ("status", "<u4")])
+
+
+class TableBatch:
+    """The request tables of a RequestBatch and the lists of one table round.  Torrent t's table
+    (and its failed list) is the .cap[t] entries from .entry_off[t]; .structs is the
+    krk_table_torrent array parallel to the batch's.  events() packs a round's lists: each a
+    {torrent: list} -- arrived pieces, gone peers, marks (piece, peer, status), holds and records
+    (piece, peer) -- a torrent that is not named has none."""
+
+    def __init__(self, batch: RequestBatch, cap=RT_MAX_ENTRIES):
+        k = len(batch)
+        self.cap = np.broadcast_to(np.asarray(cap, dtype=np.uint32), (k,)).copy()
+        self.entry_off = np.zeros(k + 1, dtype=np.uint64)
+        self.entry_off[1:] = np.cumsum(self.cap)
+        self.total_entries = int(self.entry_off[-1])
+        self.structs = (krk_table_torrent * max(k, 1))()
+        self.events()
+
+    def __len__(self):
+        return int(self.cap.size)
+
+    def events(self, arrived=None, gone=None, marks=None, holds=None, records=None):
+        k = len(self)
+        packed, offs = [], []
+        for lists, width in ((arrived, 1), (gone, 1), (marks, 3), (holds, 2), (records, 2)):
+            lists = lists or {}
+            off, rows = {}, []
+            for t in sorted(lists):
+                off[t] = (len(rows), len(lists[t]))
+                rows.extend(lists[t])
+            packed.append(np.asarray(rows, dtype=np.uint32).reshape(len(rows), width))
+            offs.append(off)
+        self.arrived, self.gone, self.marks, self.holds, self.records = packed
+        for t in range(k):
+            s = krk_table_torrent(int(self.entry_off[t]), int(self.cap[t]), 0)
+            for name, off in zip(("arrived", "gone", "mark", "hold", "record"), offs):
+                if t in off:
+                    setattr(s, name + "_off", off[t][0])
+                    setattr(s, "n_" + name + ("s" if name in ("mark", "hold", "record") else ""), off[t][1])
+            self.structs[t] = s
+        return self
+
+    def split(self, a: np.ndarray, t: int, n: int | None = None) -> np.ndarray:
+        """Torrent t's slice (its first n elements) of an array with one element a table entry."""
+        a0 = int(self.entry_off[t])
+        return a[a0:a0 + (int(self.cap[t]) if n is None else int(n))]
+
+    def lists(self):
+        """The five list pointers of a round call, in the call's order (None for an empty list)."""
+        return [a.ctypes.data if a.size else None for a in (self.arrived, self.gone, self.marks, self.holds, self.records)]
+
+
+class TableOutputs:
+    """The outputs of request_table_round_dev, in device memory or (pinned=True) in page-locked
+    host memory the kernel writes over PCIe: .quota (int32 a peer), .failed (RT_FAILED a table
+    entry) and .n_failed (uint32 a torrent; both only with failed), .n_dropped (uint32 a torrent)."""
+
+    def __init__(self, batch: RequestBatch, table: TableBatch, failed: bool = True, pinned: bool = False):
+        self.peers, self.entries, self.torrents, self.pinned = batch.total_peers, table.total_entries, len(batch), pinned
+        make = (lambda k: PinnedArray((max(k, 1),), np.uint32)) if pinned else (lambda k: DeviceBuffer(max(k, 1) * 4))
+        self.quota, self.n_dropped = make(self.peers), make(self.torrents)
+        self.failed, self.n_failed = (make(3 * self.entries), make(self.torrents)) if failed else (None, None)
+
+    def buffers(self):
+        return [b for b in (self.quota, self.failed, self.n_failed, self.n_dropped) if b is not None]
+
+    def fill(self, byte: int):
+        """Every output byte set to `byte` (tests: the call must overwrite what it owns, and only that)."""
+        for b in self.buffers():
+            if self.pinned:
+                b.a.view(np.uint8)[:] = byte
+            else:
+                b.from_host(np.full(b.nbytes, byte, dtype=np.uint8))
+
+    def to_host(self):
+        """(quota, failed or None, n_failed or None, n_dropped) as numpy arrays, once the call's stream has run."""
+        def get(b, k):
+            if b is None:
+                return None
+            return b.a[:k].copy() if self.pinned else b.to_host(np.uint32, k)
+        f = get(self.failed, 3 * self.entries)
+        return get(self.quota, self.peers).view(np.int32), None if f is None else f.view(RT_FAILED), \
+            get(self.n_failed, self.torrents), get(self.n_dropped, self.torrents)
+
+
+def request_table_round(batch: RequestBatch, table: TableBatch, bits, entries, n_entries, now: int, timeout: int,
+                        limit: int, picks=None, n_picked=None, failed: bool = True):
+    """krk_request_table_round: the whole table round on the host.  bits (uint64, the batch's
+    layout), entries (RT_ENTRY, the table's layout) and n_entries (uint32 a torrent) are updated
+    in place; picks (uint32, `limit` a peer) and n_picked are a request round's outputs, or None.
+    Returns (quota a peer, failed a table entry or None, n_failed a torrent or None, n_dropped)."""
+    for a, t in ((bits, np.uint64), (entries, RT_ENTRY), (n_entries, np.uint32)):
+        if a.dtype != t or not a.flags.c_contiguous or not a.flags.writeable:
+            raise ValueError(f"request_table_round: the state arrays are updated in place: a contiguous {t} array each")
+    if bits.size < batch.total_words or entries.size < table.total_entries or n_entries.size < len(batch):
+        raise ValueError("request_table_round: bits, entries or n_entries shorter than the batch's layout")
+    pk = None if picks is None else np.ascontiguousarray(picks, dtype=np.uint32)
+    npk = None if picks is None else np.ascontiguousarray(n_picked, dtype=np.uint32)
+    quota = np.zeros(batch.total_peers, dtype=np.int32)
+    fl = np.zeros(table.total_entries, dtype=RT_FAILED) if failed else None
+    nf = np.zeros(len(batch), dtype=np.uint32) if failed else None
+    nd = np.zeros(len(batch), dtype=np.uint32)
+    ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+    check(lib.krk_request_table_round(batch.structs, table.structs, len(batch), ptr(bits), ptr(entries), ptr(n_entries),
+                                      *table.lists(), None if pk is None else pk.ctypes.data,
+                                      None if npk is None else npk.ctypes.data, int(now), int(timeout), int(limit),
+                                      ptr(quota), fl.ctypes.data if failed else None, nf.ctypes.data if failed else None,
+                                      ptr(nd)))
+    return quota, fl, nf, nd
+
+
+def request_table_round_dev(batch: RequestBatch, table: TableBatch, bits_dev, entries_dev, n_entries_dev, now: int,
+                            timeout: int, limit: int, out: TableOutputs, picks_dev=None, n_picked_dev=None, stream=None):
+    """krk_request_table_round_dev: the table round in one call on the device, asynchronous on
+    `stream`.  bits_dev / entries_dev / n_entries_dev: DeviceBuffer or PinnedArray in the batch's
+    and the table's layout, updated where they lie; picks_dev / n_picked_dev: a request round's
+    RequestOutputs buffers, or None.  Returns out, filled once the stream has run the call."""
+    check(lib.krk_request_table_round_dev(batch.structs, table.structs, len(batch), bits_dev.ptr, entries_dev.ptr,
+                                          n_entries_dev.ptr, *table.lists(),
+                                          picks_dev.ptr if picks_dev is not None else None,
+                                          n_picked_dev.ptr if picks_dev is not None else None, int(now), int(timeout),
+                                          int(limit), out.quota.ptr, out.failed.ptr if out.failed is not None else None,
+                                          out.n_failed.ptr if out.failed is not None else None, out.n_dropped.ptr, stream))
+    return out
+
+
+def request_table_geometry():
+    """(the entries one step of the table compaction takes, the keys one workgroup sorts in LDS:
+    the most entries a table holds)."""
+    c, t = C.c_uint64(), C.c_uint64()
+    check(lib.krk_request_table_geometry(C.byref(c), C.byref(t)))
+    return int(c.value), int(t.value)
 
 
 AN_MAX_WINDOWS, AN_MAX_ORIGINS, AN_MAX_LIMIT = 8, 8, 64

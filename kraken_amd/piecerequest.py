@@ -321,3 +321,149 @@ def ResendRound(dispatchers, placement: str = "host"):
             got.append((r, peerID))
         out.append(got)
     return out
+
+
+class RequestTable:
+    """The request tables of a set of dispatchers kept where the rounds read them
+    (``krk_request_table_round`` / ``krk_request_table_round_dev``): the rows (have, then
+    (bitfield, blocked) a peer) and one table of up to `cap` requests a torrent are uploaded once --
+    placement "gpu": into device memory; "host": numpy arrays and the host forms -- and after that
+    only a round's event lists cross the link.  The dispatchers give the shapes, the peers' order
+    and bitfields, and their managers the clock, the timeout, the policy, the pipeline limit and
+    the seeds (drawn exactly as ``ReserveRound`` draws them); the managers' own request maps are
+    not used.  Events are queued on the host and applied by the next round.  A removed peer keeps
+    its index: its row is zeroed and its requests dropped -- all of them, where the reference's
+    ClearPeer leaves all but the first a piece behind (manager.go:188-196)."""
+
+    def __init__(self, dispatchers, placement: str = "host", cap: int = D.RT_MAX_ENTRIES):
+        if placement not in ("host", "gpu"):
+            raise ValueError(f"RequestTable: placement {placement!r} is neither \"host\" nor \"gpu\"")
+        self.ds, self.gpu = list(dispatchers), placement == "gpu"
+        limits = {d.manager.pipelineLimit for d in self.ds}
+        if len(limits) != 1:
+            raise ValueError(f"RequestTable: one pipeline limit a table, got {sorted(limits)}")
+        self.limit = limits.pop()
+        self.peers = [list(d.peers) for d in self.ds]
+        self.index = [{peerID: p for p, peerID in enumerate(ps)} for ps in self.peers]
+        self.have = [d.have.copy() for d in self.ds]  # the host's count of the arrived pieces: the endgame rule
+        self._layout([d.manager.policy for d in self.ds], 0)
+        self.table = D.TableBatch(self.batch, cap)
+        bits = np.zeros(max(self.batch.total_words, 1), dtype=np.uint64)
+        for t, d in enumerate(self.ds):
+            rows = self.batch.rows(bits, t)
+            rows[0] = bitset_words(d.have)
+            for p, b in enumerate(d.peers.values()):
+                rows[1 + 2 * p] = bitset_words(b)
+        entries = np.zeros(max(self.table.total_entries, 1), dtype=D.RT_ENTRY)
+        n_entries = np.zeros(len(self.ds), dtype=np.uint32)
+        if self.gpu:
+            self.bits, self.entries, self.n_entries = (D.DeviceBuffer(a.nbytes) for a in (bits, entries, n_entries))
+            for buf, a in ((self.bits, bits), (self.entries, entries), (self.n_entries, n_entries)):
+                buf.from_host(a)
+            self.out = D.TableOutputs(self.batch, self.table, failed=True, pinned=False)
+            self.failed = D.TableOutputs(self.batch, self.table, failed=True, pinned=True)  # Resend's list, page-locked
+            self.picks = D.RequestOutputs(self.batch, self.limit)  # in HBM: recorded there, copied down once
+        else:
+            self.bits, self.entries, self.n_entries = bits, entries, n_entries
+        self._events = {name: {} for name in ("arrived", "gone", "marks", "holds")}
+
+    def _layout(self, flags, seeds):
+        self.batch = D.RequestBatch([d.n_pieces for d in self.ds], [len(ps) for ps in self.peers], flags, seeds)
+
+    # -- events, queued until the next round
+    def Arrived(self, t: int, pieces):
+        """The pieces have arrived: set in have, their requests cleared (Manager.Clear)."""
+        new = [int(i) for i in pieces if not self.have[t][int(i)]]
+        self.have[t][new] = True
+        self._events["arrived"].setdefault(t, set()).update(new)
+
+    def Announced(self, t: int, peerID, pieces):
+        """The peer announced the pieces (handleAnnouncePiece)."""
+        p = self.index[t][peerID]
+        self._events["holds"].setdefault(t, set()).update((int(i), p) for i in pieces)
+
+    def MarkUnsent(self, t: int, peerID, i: int):
+        self._events["marks"].setdefault(t, []).append((int(i), self.index[t][peerID], StatusUnsent))
+
+    def MarkInvalid(self, t: int, peerID, i: int):
+        self._events["marks"].setdefault(t, []).append((int(i), self.index[t][peerID], StatusInvalid))
+
+    def RemovePeer(self, t: int, peerID):
+        self._events["gone"].setdefault(t, set()).add(self.index[t][peerID])
+
+    def endgame(self, t: int) -> bool:
+        d = self.ds[t]
+        return not d.disable_endgame and d.n_pieces - int(self.have[t].sum()) <= d.endgame_threshold
+
+    # -- rounds
+    def _round(self, out=None, records=None, picks=None):
+        """One table round at the dispatchers' clock: the queued events, `records`, the picks."""
+        ev, self._events = self._events, {name: {} for name in self._events}
+        self.table.events(arrived={t: sorted(s) for t, s in ev["arrived"].items()},
+                          gone={t: sorted(s) for t, s in ev["gone"].items()}, marks=ev["marks"],
+                          holds={t: sorted(s, key=lambda h: h[::-1]) for t, s in ev["holds"].items()}, records=records)
+        clocks = {(d.manager.clock.Now(), d.manager.timeout) for d in self.ds}
+        if len(clocks) != 1:
+            raise ValueError("RequestTable: the dispatchers of a round share one clock reading and one timeout")
+        now, timeout = clocks.pop()
+        if self.gpu:
+            D.request_table_round_dev(self.batch, self.table, self.bits, self.entries, self.n_entries, now, timeout,
+                                      self.limit, out or self.out, picks_dev=picks.picks if picks else None,
+                                      n_picked_dev=picks.n_picked if picks else None)
+            return None
+        return D.request_table_round(self.batch, self.table, self.bits, self.entries, self.n_entries, now, timeout,
+                                     self.limit, picks=picks[0] if picks else None, n_picked=picks[1] if picks else None)
+
+    def Reserve(self):
+        """ReserveRound over the resident tables: a table round (the events, then quotas and blocked
+        rows derived where they lie), the request round on them, and a table round that records its
+        picks from where the request round left them.  Returns one {peerID: [pieces]} a torrent."""
+        if not self.ds:
+            return []
+        dups = [self.endgame(t) for t in range(len(self.ds))]
+        flags = [d.manager.policy | (D.PR_ALLOW_DUPLICATES if dup else 0) for d, dup in zip(self.ds, dups)]
+        self._layout(flags, [d.manager.next_seed() if d.manager.policy == D.PR_SAMPLE else 0 for d in self.ds])
+        if self.gpu:
+            self._round()
+            D.piece_request_round_dev(self.batch, self.bits, self.out.quota, self.limit, out=self.picks)
+            self._round(picks=self.picks)
+            D.check(D.lib.krk_stream_sync(None))
+            _, picks, n_picked = self.picks.to_host()
+        else:
+            quota = self._round()[0]
+            _, picks, n_picked = D.piece_request_round(self.batch, self.bits, quota, self.limit)
+            self._round(picks=(picks, n_picked))
+        return [{peerID: picks[int(self.batch.peer_off[t]) + p, :int(n_picked[int(self.batch.peer_off[t]) + p])].tolist()
+                 for p, peerID in enumerate(ps)} for t, ps in enumerate(self.peers)]
+
+    def Resend(self):
+        """ResendRound over the resident tables: a table round that leaves the failed list in
+        page-locked memory (one stream synchronise), the resend round on the resident rows, and a
+        table round that records the targets.  Returns one [(Request, target peerID or None)] a
+        torrent; the Request's PeerID is the peer the request failed on."""
+        if not self.ds:
+            return []
+        dups = [self.endgame(t) for t in range(len(self.ds))]
+        self._layout([d.manager.policy | (D.PR_ALLOW_DUPLICATES if dup else 0) for d, dup in zip(self.ds, dups)], 0)
+        if self.gpu:
+            self._round(out=self.failed)
+            D.check(D.lib.krk_stream_sync(None))
+            quota, failed, n_failed, _ = self.failed.quota, *self.failed.to_host()[1:]
+        else:
+            quota, failed, n_failed, _ = self._round()
+        lists = [[tuple(int(x) for x in f) for f in self.table.split(failed, t, n_failed[t])] for t in range(len(self.ds))]
+        resend = D.ResendBatch(self.batch, lists)
+        if self.gpu:
+            target, _, _ = D.piece_resend_round_dev(self.batch, resend, self.bits, quota, quota_left=False)
+        else:
+            target, _, _ = D.piece_resend_round(self.batch, resend, self.bits, quota, quota_left=False)
+        out, records = [], {}
+        for t, fl in enumerate(lists):
+            got = []
+            for (piece, peer, status), p in zip(fl, resend.split(target, t).tolist()):
+                if p != D.PR_NONE:
+                    records.setdefault(t, []).append((piece, p))
+                got.append((Request(piece, self.peers[t][peer], status), None if p == D.PR_NONE else self.peers[t][p]))
+            out.append(got)
+        self._round(records=records)
+        return out
