@@ -452,6 +452,99 @@ int krk_request_table_round_dev(const krk_request_torrent* torrents_host, const 
                                 int32_t* quota_out, krk_failed_request* failed_out, uint32_t* n_failed_out,
                                 uint32_t* n_dropped_out, void* stream);
 
+/* ------------------------------------------- peer rounds
+ * The peer set of the resident rows and the progress the dispatcher derives from them:
+ * Dispatcher.AddPeer from the wire bytes of the handshake's BitfieldMessage
+ * (lib/torrent/scheduler/conn/handshaker.go:63-131, dispatch/dispatcher.go:243-274),
+ * handleComplete (dispatcher.go:589-597), the endgame rule (:366-372) and complete() (:321-338).
+ * A torrent is its krk_request_torrent, unchanged: only n_pieces, n_peers, bits_off and peer_off
+ * are read, and n_peers counts peer SLOTS -- rows that a connection may or may not occupy.  Its
+ * krk_peer_torrent names its live row (ceil(n_peers / 64) words at live[live_off ..]: bit p & 63 of
+ * word p >> 6 is set iff slot p holds a connection) and its two lists.  With W =
+ * krk_bitfield_words(n_pieces) and mask = the bits below n_pieces, one round runs in this order:
+ *   1 joins  krk_peer_join, strictly ascending by peer (at most one a slot a round).
+ *            wire[wire_off .. wire_off + wire_len) is a willf/bitset MarshalBinary: a uint64
+ *            big-endian bit length, then ceil(length / 64) words, each uint64 big-endian, word k
+ *            holding bits 64k .. 64k + 63.  This is the format of the willf/bitset commit that the
+ *            reference's glide.lock names; its source is not part of this tree, so it is the
+ *            format ASSUMED, pinned by: bits {0, 9} of 10 pieces are the 16 bytes
+ *            00 00 00 00 00 00 00 0A  00 00 00 00 00 00 02 01.
+ *            Well formed iff wire_len >= 8, the length field equals n_pieces and wire_len ==
+ *            8 + 8 W: bits_p becomes the decoded words with the tail bits past n_pieces cleared,
+ *            and KRK_PE_JOINED is set.  Otherwise KRK_PE_BAD_BITFIELD, and the row keeps every bit:
+ *            the bytes come from a remote peer, so a malformed wire is that peer's status and never
+ *            KRK_EINVAL.  wire_off is any byte offset; no byte outside the span is read.
+ *   2 fulls  peers, strictly ascending: bits_p becomes all ones below n_pieces, the tail clear,
+ *            and KRK_PE_SET_FULL is set.  A peer joined and filled in one round ends up full,
+ *            with both bits.
+ *   3 derive remaining_out[t] = n_pieces - popcount(have & mask);
+ *            torrent_flags_out[t] = KRK_PE_TORRENT_COMPLETE iff remaining is 0, KRK_PE_ENDGAME iff
+ *            KRK_PE_DISABLE_ENDGAME is not set and remaining <= endgame_threshold;
+ *            for every slot p: held_out[peer_off + p] = popcount(bits_p & mask),
+ *            wanted_out[peer_off + p] = popcount(bits_p & ~have & mask) (the size of
+ *            maybeRequestMorePieces' candidate set: 0 means nothing to ask this peer), and
+ *            status_out[peer_off + p] = the bits above, plus, for a slot whose live bit is set
+ *            only: KRK_PE_PEER_COMPLETE iff held == n_pieces, and under a complete torrent
+ *            KRK_PE_CLOSE for a complete peer, KRK_PE_NOTIFY for any other.
+ * A zero-piece torrent is complete and so is each of its live peers.  blocked_p is not touched (the
+ * table round derives it), and neither is `live`: the caller sets a slot's bit when it queues the
+ * join and clears it with the table round's `gone`.  A slot freed by `gone` may be joined in a
+ * later peer round, never in the same step's: the caller orders the two.
+ *
+ * bits is read and written; every remaining_out and torrent_flags_out element a torrent, and every
+ * held_out, wanted_out and status_out element a slot, is stored by the call: the caller pre-zeroes
+ * nothing.  KRK_EINVAL, refused before anything is touched: a list that does not ascend strictly,
+ * a peer >= n_peers, a non-zero reserved field, an unknown bit in krk_peer_torrent.flags,
+ * wire_off + wire_len overflowing, n_pieces >= 2^32, an offset of 2^48 or more, a NULL that is
+ * not nullable (bits with no words, live and the per-slot outputs with no slots, joins, fulls and
+ * wire with nothing to read are).  The regions the torrents name in one array must not overlap. */
+#define KRK_PE_DISABLE_ENDGAME 1u   /* krk_peer_torrent.flags: Config.DisableEndgame */
+/* torrent_flags_out */
+#define KRK_PE_TORRENT_COMPLETE 1u
+#define KRK_PE_ENDGAME 2u
+/* status_out, one word a peer slot */
+#define KRK_PE_JOINED 0x01u         /* a join of this round wrote the row */
+#define KRK_PE_BAD_BITFIELD 0x02u   /* a join of this round was malformed: row untouched */
+#define KRK_PE_SET_FULL 0x04u       /* a Complete message of this round filled the row */
+#define KRK_PE_PEER_COMPLETE 0x08u  /* live and held == n_pieces */
+#define KRK_PE_CLOSE 0x10u          /* live, torrent complete, peer complete: complete() closes it */
+#define KRK_PE_NOTIFY 0x20u         /* live, torrent complete, peer not: complete() sends Complete */
+typedef struct {
+    uint32_t endgame_threshold; /* Config.EndgameThreshold */
+    uint32_t flags;
+    uint64_t live_off;          /* first word of its live row in `live` */
+    uint64_t join_off;          /* first entry in `joins` */
+    uint64_t full_off;          /* first entry in `fulls` */
+    uint32_t n_joins;
+    uint32_t n_fulls;
+} krk_peer_torrent;             /* parallel to torrents[] */
+typedef struct {
+    uint32_t peer;
+    uint32_t reserved;          /* 0 */
+    uint64_t wire_off;          /* any byte offset in `wire` */
+    uint64_t wire_len;
+} krk_peer_join;
+/* The whole round of n_torrents torrents on the host.  No device. */
+int krk_peer_round(const krk_request_torrent* torrents, const krk_peer_torrent* peer_torrents, uint64_t n_torrents,
+                   uint64_t* bits, const uint64_t* live, const krk_peer_join* joins, const uint32_t* fulls,
+                   const uint8_t* wire, uint32_t* remaining_out, uint32_t* torrent_flags_out, uint32_t* held_out,
+                   uint32_t* wanted_out, uint32_t* status_out);
+/* The same on the device (peer_round.hip), bit for bit; asynchronous on `stream`: one launch, one
+ * wave a row.  bits_dev (8-byte aligned), wire_dev (any byte alignment) and the five outputs
+ * (4-byte aligned) are device memory or page-locked host memory (krk_host_alloc): anything else is
+ * KRK_EINVAL before anything is launched.  torrents_host, peer_torrents_host, live_host,
+ * joins_host and fulls_host are host memory: the lists are checked as above, and all of them are
+ * copied into the library's staging as one block, before the call returns.  The wire bytes are
+ * read by the kernel, where they lie, once the stream reaches the call; every span, a malformed
+ * one included, lies inside wire_dev's allocation (the caller cut it from a message it received:
+ * anything else is KRK_EINVAL).  n_torrents == 0 is
+ * KRK_OK; KRK_ENODEV without a gfx950 device: there is no fall-back to the host form. */
+int krk_peer_round_dev(const krk_request_torrent* torrents_host, const krk_peer_torrent* peer_torrents_host,
+                       uint64_t n_torrents, uint64_t* bits_dev, const uint64_t* live_host,
+                       const krk_peer_join* joins_host, const uint32_t* fulls_host, const uint8_t* wire_dev,
+                       uint32_t* remaining_out, uint32_t* torrent_flags_out, uint32_t* held_out, uint32_t* wanted_out,
+                       uint32_t* status_out, void* stream);
+
 /* ------------------------------------------- announce rounds
  * Whom an announcing peer talks to: the tracker's announce (tracker/trackerserver/announce.go:75-115)
  * for a batch of announces at one clock instant -- peerstore UpdatePeer and GetPeers

@@ -272,6 +272,11 @@ int krk_piece_resend_geometry(uint64_t* peers_per_pass);
  * the same size) and the keys one workgroup sorts in LDS (the most entries a table holds) -- for
  * the tests that pin krk_request_table_round_dev's edges.  No device. */
 int krk_request_table_geometry(uint64_t* chunk, uint64_t* tile);
+/* The shape of peer_round.hip as built (kernel name "peer_round"): the most units (rows: one
+ * `have` and one a peer slot a torrent) a launch gives a wave of their own -- beyond it the waves
+ * stride -- and the row words one lane takes in a step (a wave covers 64 times that) -- for the
+ * tests that pin krk_peer_round_dev's edges.  No device. */
+int krk_peer_round_geometry(uint64_t* unit_cap, uint64_t* lane_words);
 /* The shape of the SHA-256 host share as built (offload.cpp): the bytes of one device-to-host copy
  * (a chain longer than that comes down in several), the pinned buffers an offload thread's copy
  * ring has (a chain of more chunks than that wraps it) and those of a resumer

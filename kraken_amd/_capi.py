@@ -21,6 +21,8 @@ KRK_OFFLOAD_AUTO = -1
 KRK_PR_MAX_LIMIT, KRK_PR_RAREST_FIRST, KRK_PR_SAMPLE, KRK_PR_ALLOW_DUPLICATES, KRK_PR_NONE = 16, 0, 1, 0x100, 0xFFFFFFFF
 KRK_PR_EXPIRED, KRK_PR_UNSENT, KRK_PR_INVALID = 1, 2, 3
 KRK_RT_MAX_ENTRIES = 4096
+KRK_PE_DISABLE_ENDGAME, KRK_PE_TORRENT_COMPLETE, KRK_PE_ENDGAME = 1, 1, 2
+KRK_PE_JOINED, KRK_PE_BAD_BITFIELD, KRK_PE_SET_FULL, KRK_PE_PEER_COMPLETE, KRK_PE_CLOSE, KRK_PE_NOTIFY = 1, 2, 4, 8, 16, 32
 KRK_AN_MAX_WINDOWS, KRK_AN_MAX_ORIGINS, KRK_AN_MAX_LIMIT = 8, 8, 64
 KRK_AN_DEFAULT, KRK_AN_COMPLETENESS, KRK_AN_COMPLETE = 0, 1, 1
 KRK_AN_NONE, KRK_AN_ORIGIN, KRK_AN_COMPLETE_BIT = 0xFFFFFFFF, 0x80000000, 0x40000000
@@ -89,6 +91,15 @@ class krk_table_torrent(C.Structure):
                 ("arrived_off", C.c_uint64), ("n_arrived", C.c_uint64), ("gone_off", C.c_uint64), ("n_gone", C.c_uint64),
                 ("mark_off", C.c_uint64), ("n_marks", C.c_uint64), ("hold_off", C.c_uint64), ("n_holds", C.c_uint64),
                 ("record_off", C.c_uint64), ("n_records", C.c_uint64)]
+
+
+class krk_peer_torrent(C.Structure):
+    _fields_ = [("endgame_threshold", C.c_uint32), ("flags", C.c_uint32), ("live_off", C.c_uint64), ("join_off", C.c_uint64),
+                ("full_off", C.c_uint64), ("n_joins", C.c_uint32), ("n_fulls", C.c_uint32)]
+
+
+class krk_peer_join(C.Structure):
+    _fields_ = [("peer", C.c_uint32), ("reserved", C.c_uint32), ("wire_off", C.c_uint64), ("wire_len", C.c_uint64)]
 
 
 class krk_announce_torrent(C.Structure):
@@ -201,6 +212,11 @@ def _load() -> C.CDLL:
                                             vp, vp, vp, vp, vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_uint32, vp, vp, vp, vp,
                                             vp]),
         "krk_request_table_geometry": (i, [u64p, u64p]),
+        "krk_peer_round": (i, [C.POINTER(krk_request_torrent), C.POINTER(krk_peer_torrent), C.c_uint64, vp, vp, vp, vp, vp,
+                               vp, vp, vp, vp, vp]),
+        "krk_peer_round_dev": (i, [C.POINTER(krk_request_torrent), C.POINTER(krk_peer_torrent), C.c_uint64, vp, vp, vp, vp,
+                                   vp, vp, vp, vp, vp, vp, vp]),
+        "krk_peer_round_geometry": (i, [u64p, u64p]),
         "krk_announce_handout": (i, [C.POINTER(krk_announce_torrent), C.c_uint64, u64p, C.POINTER(krk_announce), C.c_uint32,
                                      C.c_uint32, u32p, u32p, u32p]),
         "krk_announce_round": (i, [C.POINTER(krk_announce_torrent), C.c_uint64, u64p, C.POINTER(krk_announce), C.c_uint64,

@@ -448,6 +448,34 @@ hipError_t launch_request_table(const RtTorrent* tors, uint64_t n_tors, const ui
                                 rt::Entry* entries, uint32_t* n_entries, int32_t* quota, rs::Failed* failed,
                                 uint32_t* n_failed, uint32_t* n_dropped, hipStream_t s);
 
+// One torrent of a peer round (peer_round.hip, peer_round_math.hpp): its rows as a request
+// round's, its units [first_unit, first_unit + 1 + n_peers) -- `have`, then one a peer slot -- its
+// per-slot outputs from peer_off, and its staged live words (uint64), joins (pe::Join, wire_off an
+// offset in the caller's wire array) and fulls (uint32) from live_at / join_at / full_at.
+namespace pe {
+struct Join;
+}
+struct alignas(16) PeTorrent {
+    uint64_t first_unit;
+    uint64_t n_pieces;  // < 2^32
+    uint64_t bits_off;
+    uint64_t peer_off;
+    uint64_t live_at, join_at, full_at;
+    uint32_t n_peers, n_joins, n_fulls;
+    uint32_t threshold;
+    uint32_t flags;  // pe::kDisableEndgame
+    uint32_t pad;
+};
+static_assert(sizeof(PeTorrent) == 80, "PeTorrent layout");
+constexpr uint32_t kPeUnitCap = 16384;  // the units a launch gives a wave of their own: 4,096 workgroups
+constexpr uint32_t kPeLaneWords = 4;    // the row words a lane takes in a step: a wave covers 256
+// One wave a unit: the joins and fulls applied to bits, every remaining / tflags element a torrent
+// and every held / wanted / status element a slot stored.  The lists are valid (pe::lists_error).
+hipError_t launch_peer_round(const PeTorrent* tors, uint64_t n_tors, uint64_t n_units, const uint64_t* live,
+                             const pe::Join* joins, const uint32_t* fulls, const uint8_t* wire, uint64_t* bits,
+                             uint32_t* remaining, uint32_t* tflags, uint32_t* held, uint32_t* wanted, uint32_t* status,
+                             hipStream_t s);
+
 // ---------------------------------------------------------------- announce rounds
 // One announce round (announce_round.hip, announce_math.hpp): the update launch sets every
 // announcer's bits in window 0 of its torrent (atomic or), the handout launch -- one wave an

@@ -8,7 +8,7 @@ import os
 import numpy as np
 
 from ._capi import (check, krk_blob, krk_file_blob, krk_chunk, krk_launch_rec, krk_nodes, krk_planner_rates,
-                    krk_request_torrent, krk_resend_torrent, krk_failed_request, krk_table_torrent, krk_announce_torrent, krk_announce, krk_conn_torrent,
+                    krk_request_torrent, krk_resend_torrent, krk_failed_request, krk_table_torrent, krk_peer_torrent, krk_announce_torrent, krk_announce, krk_conn_torrent,
                     krk_conn_lists, krk_conn_transition, krk_conn_incoming, lib)
 
 ALIGN = 256  # every blob starts 256-byte aligned in the arena
@@ -1177,6 +1177,108 @@ def request_table_geometry():
     c, t = C.c_uint64(), C.c_uint64()
     check(lib.krk_request_table_geometry(C.byref(c), C.byref(t)))
     return int(c.value), int(t.value)
+
+
+# ------------------------------------------------------------------ peer rounds
+PE_DISABLE_ENDGAME, PE_TORRENT_COMPLETE, PE_ENDGAME = 1, 1, 2
+PE_JOINED, PE_BAD_BITFIELD, PE_SET_FULL, PE_PEER_COMPLETE, PE_CLOSE, PE_NOTIFY = 1, 2, 4, 8, 16, 32
+PE_JOIN = np.dtype([("peer", "<u4"), ("reserved", "<u4"), ("wire_off", "<u8"), ("wire_len", "<u8")])
+
+
+class PeerBatch:
+    """The peer slots of a RequestBatch and the lists of one peer round.  .structs is the
+    krk_peer_torrent array parallel to the batch's; .live the packed live words, torrent t's row
+    (ceil(n_peers / 64) words) from .live_off[t]; set_live() flips a slot's bit.  events() packs a
+    round's lists: joins {torrent: [(slot, wire bytes)]} and fulls {torrent: [slot]}, both ascending
+    by slot -- a torrent that is not named has none.  The wire spans lie back to back in .wire
+    (uint8), at whatever byte they fall."""
+
+    def __init__(self, batch: RequestBatch, endgame_threshold=0, flags=0, live=None):
+        k = len(batch)
+        self.threshold = np.broadcast_to(np.asarray(endgame_threshold, dtype=np.uint32), (k,)).copy()
+        self.flags = np.broadcast_to(np.asarray(flags, dtype=np.uint32), (k,)).copy()
+        self.live_off = np.zeros(k + 1, dtype=np.uint64)
+        self.live_off[1:] = np.cumsum((batch.n_peers.astype(np.uint64) + np.uint64(63)) // np.uint64(64))
+        self.live = np.zeros(max(int(self.live_off[-1]), 1), dtype=np.uint64)
+        for t, slots in enumerate(live or ()):
+            for p in slots:
+                self.set_live(t, p)
+        self.structs = (krk_peer_torrent * max(k, 1))()
+        self.events()
+
+    def __len__(self):
+        return int(self.threshold.size)
+
+    def set_live(self, t: int, p: int, on: bool = True):
+        w, bit = int(self.live_off[t]) + (p >> 6), np.uint64(1 << (p & 63))
+        self.live[w] = (self.live[w] | bit) if on else (self.live[w] & ~bit)
+
+    def events(self, joins=None, fulls=None):
+        joins, fulls = joins or {}, fulls or {}
+        rows, full_rows, wire = [], [], bytearray()
+        for t in range(len(self)):
+            s = krk_peer_torrent(int(self.threshold[t]), int(self.flags[t]), int(self.live_off[t]), len(rows), len(full_rows),
+                                 len(joins.get(t, ())), len(fulls.get(t, ())))
+            for p, span in joins.get(t, ()):
+                rows.append((p, 0, len(wire), len(span)))
+                wire += span
+            full_rows.extend(fulls.get(t, ()))
+            self.structs[t] = s
+        self.joins, self.fulls = np.array(rows, dtype=PE_JOIN), np.asarray(full_rows, dtype=np.uint32)
+        self.wire = np.frombuffer(bytes(wire), dtype=np.uint8)
+        return self
+
+    def lists(self):
+        """(live, joins, fulls) pointers of a round call (None for an empty list)."""
+        return [a.ctypes.data if a.size else None for a in (self.live, self.joins, self.fulls)]
+
+
+class PeerOutputs:
+    """The outputs of peer_round_dev, in device memory or (pinned=True) in page-locked host memory
+    the kernel writes over PCIe: .remaining and .tflags (uint32 a torrent), .held, .wanted and
+    .status (uint32 a peer slot)."""
+    NAMES = ("remaining", "tflags", "held", "wanted", "status")
+
+    def __init__(self, batch: RequestBatch, pinned: bool = False):
+        self.peers, self.torrents, self.pinned = batch.total_peers, len(batch), pinned
+        make = (lambda k: PinnedArray((max(k, 1),), np.uint32)) if pinned else (lambda k: DeviceBuffer(max(k, 1) * 4))
+        self.remaining, self.tflags = make(self.torrents), make(self.torrents)
+        self.held, self.wanted, self.status = make(self.peers), make(self.peers), make(self.peers)
+
+    def to_host(self):
+        """(remaining, tflags, held, wanted, status) as numpy arrays, once the call's stream has run."""
+        sizes = (self.torrents, self.torrents, self.peers, self.peers, self.peers)
+        return tuple(b.a[:k].copy() if self.pinned else b.to_host(np.uint32, k)
+                     for b, k in zip((getattr(self, n) for n in self.NAMES), sizes))
+
+
+def peer_round(batch: RequestBatch, peers: PeerBatch, bits):
+    """krk_peer_round: the whole peer round on the host.  bits (uint64, the batch's layout) is
+    updated in place.  Returns (remaining, tflags a torrent; held, wanted, status a peer slot)."""
+    if bits.dtype != np.uint64 or not bits.flags.c_contiguous or not bits.flags.writeable or bits.size < batch.total_words:
+        raise ValueError("peer_round: bits is updated in place: a contiguous uint64 array in the batch's layout")
+    out = [np.zeros(max(k, 1), dtype=np.uint32) for k in (len(batch),) * 2 + (batch.total_peers,) * 3]
+    check(lib.krk_peer_round(batch.structs, peers.structs, len(batch), bits.ctypes.data if bits.size else None, *peers.lists(),
+                             peers.wire.ctypes.data if peers.wire.size else None, *(a.ctypes.data for a in out)))
+    return tuple(a[:k] for a, k in zip(out, (len(batch),) * 2 + (batch.total_peers,) * 3))
+
+
+def peer_round_dev(batch: RequestBatch, peers: PeerBatch, bits_dev, wire_dev, out: PeerOutputs, stream=None):
+    """krk_peer_round_dev: the peer round in one call on the device, asynchronous on `stream`.
+    bits_dev: DeviceBuffer or PinnedArray in the batch's layout, updated where it lies; wire_dev:
+    the bytes of peers.wire in a DeviceBuffer or PinnedArray (None when no join is queued).
+    Returns out, filled once the stream has run the call."""
+    check(lib.krk_peer_round_dev(batch.structs, peers.structs, len(batch), bits_dev.ptr, *peers.lists(),
+                                 wire_dev.ptr if wire_dev is not None else None,
+                                 *(getattr(out, n).ptr for n in out.NAMES), stream))
+    return out
+
+
+def peer_round_geometry():
+    """(the units -- rows -- a launch gives a wave of their own, the row words a lane takes in a step)."""
+    c, s = C.c_uint64(), C.c_uint64()
+    check(lib.krk_peer_round_geometry(C.byref(c), C.byref(s)))
+    return int(c.value), int(s.value)
 
 
 AN_MAX_WINDOWS, AN_MAX_ORIGINS, AN_MAX_LIMIT = 8, 8, 64

@@ -47,6 +47,14 @@ def bitset_words(bools) -> np.ndarray:
     return np.concatenate([b, np.zeros(-b.size % 8, dtype=np.uint8)]).view(np.uint64)
 
 
+def marshal_bitfield(bools) -> bytes:
+    """The wire form of a peer's bitfield, as the handshake's BitfieldMessage carries it: a
+    willf/bitset MarshalBinary -- the bit length as a big-endian uint64, then the words, each a
+    big-endian uint64."""
+    b = np.asarray(bools, dtype=bool)
+    return int(b.size).to_bytes(8, "big") + bitset_words(b).astype(">u8").tobytes()
+
+
 class MockClock:
     """clock.NewMock(): stands still until Add."""
 
@@ -333,9 +341,15 @@ class RequestTable:
     the seeds (drawn exactly as ``ReserveRound`` draws them); the managers' own request maps are
     not used.  Events are queued on the host and applied by the next round.  A removed peer keeps
     its index: its row is zeroed and its requests dropped -- all of them, where the reference's
-    ClearPeer leaves all but the first a piece behind (manager.go:188-196)."""
+    ClearPeer leaves all but the first a piece behind (manager.go:188-196).
 
-    def __init__(self, dispatchers, placement: str = "host", cap: int = D.RT_MAX_ENTRIES):
+    The peer set changes where the rows lie (``krk_peer_round`` / ``krk_peer_round_dev``): every
+    torrent's layout has `spare_peers` empty slots after its peers, ``AddPeer`` queues a join from
+    the handshake's wire bytes into the lowest free slot, ``PeerComplete`` queues a Complete
+    message, and ``Progress`` reads what the dispatcher derives from the rows.  A removed peer's
+    slot is free again once a round has applied the removal."""
+
+    def __init__(self, dispatchers, placement: str = "host", cap: int = D.RT_MAX_ENTRIES, spare_peers: int = 0):
         if placement not in ("host", "gpu"):
             raise ValueError(f"RequestTable: placement {placement!r} is neither \"host\" nor \"gpu\"")
         self.ds, self.gpu = list(dispatchers), placement == "gpu"
@@ -343,8 +357,8 @@ class RequestTable:
         if len(limits) != 1:
             raise ValueError(f"RequestTable: one pipeline limit a table, got {sorted(limits)}")
         self.limit = limits.pop()
-        self.peers = [list(d.peers) for d in self.ds]
-        self.index = [{peerID: p for p, peerID in enumerate(ps)} for ps in self.peers]
+        self.peers = [list(d.peers) + [None] * int(spare_peers) for d in self.ds]  # a slot's peerID, None while free
+        self.index = [{peerID: p for p, peerID in enumerate(d.peers)} for d in self.ds]
         self.have = [d.have.copy() for d in self.ds]  # the host's count of the arrived pieces: the endgame rule
         self._layout([d.manager.policy for d in self.ds], 0)
         self.table = D.TableBatch(self.batch, cap)
@@ -366,6 +380,14 @@ class RequestTable:
         else:
             self.bits, self.entries, self.n_entries = bits, entries, n_entries
         self._events = {name: {} for name in ("arrived", "gone", "marks", "holds")}
+        self.slots = D.PeerBatch(self.batch, [d.endgame_threshold for d in self.ds],
+                                 [D.PE_DISABLE_ENDGAME if d.disable_endgame else 0 for d in self.ds],
+                                 live=[range(len(d.peers)) for d in self.ds])
+        self._joins, self._fulls = {}, {}  # {torrent: {slot: wire}}, {torrent: {slot}}
+        self._refused = [[] for _ in self.ds]
+        if self.gpu:
+            self.progress = D.PeerOutputs(self.batch, pinned=True)  # read after one synchronise
+            self._wire = D.DeviceBuffer(1 << 12)
 
     def _layout(self, flags, seeds):
         self.batch = D.RequestBatch([d.n_pieces for d in self.ds], [len(ps) for ps in self.peers], flags, seeds)
@@ -389,16 +411,93 @@ class RequestTable:
         self._events["marks"].setdefault(t, []).append((int(i), self.index[t][peerID], StatusInvalid))
 
     def RemovePeer(self, t: int, peerID):
-        self._events["gone"].setdefault(t, set()).add(self.index[t][peerID])
+        p = self.index[t].pop(peerID)
+        self.slots.set_live(t, p, False)
+        self._fulls.get(t, set()).discard(p)
+        if self._joins.get(t, {}).pop(p, None) is not None:
+            self.peers[t][p] = None  # never joined: nothing to drop, the slot is free at once
+        else:
+            self._events["gone"].setdefault(t, set()).add(p)  # peers[t][p] stays until a round has applied it
+
+    def AddPeer(self, t: int, peerID, wire: bytes):
+        """Dispatcher.AddPeer from the handshake: the peer takes the lowest free slot, its bitfield
+        decoded from `wire` (``marshal_bitfield``'s form) by the next peer round."""
+        if peerID in self.index[t]:
+            raise ValueError("peer already exists")
+        free = [p for p, x in enumerate(self.peers[t]) if x is None]
+        if not free:
+            raise ValueError("no free peer slot")
+        self.peers[t][free[0]], self.index[t][peerID] = peerID, free[0]
+        self.slots.set_live(t, free[0])
+        self._joins.setdefault(t, {})[free[0]] = bytes(wire)
+
+    def PeerComplete(self, t: int, peerID):
+        """The peer sent Complete (handleComplete): it holds every piece."""
+        self._fulls.setdefault(t, set()).add(self.index[t][peerID])
 
     def endgame(self, t: int) -> bool:
         d = self.ds[t]
         return not d.disable_endgame and d.n_pieces - int(self.have[t].sum()) <= d.endgame_threshold
 
     # -- rounds
+    def _peer_round(self, always=False):
+        """One peer round over the queued joins and fulls (none queued: only when `always`).  The
+        joins' statuses are read back: a peer whose bitfield was malformed leaves the index again.
+        Returns the five outputs when they were read (after one synchronise), else None."""
+        if not (self._joins or self._fulls or always):
+            return None
+        joins, self._joins = self._joins, {}
+        fulls, self._fulls = self._fulls, {}
+        self.slots.events({t: sorted(j.items()) for t, j in joins.items()}, {t: sorted(f) for t, f in fulls.items()})
+        if self.gpu:
+            if self.slots.wire.size > self._wire.nbytes:
+                self._wire = D.DeviceBuffer(2 * self.slots.wire.size)
+            self._wire.from_host(self.slots.wire)
+            D.peer_round_dev(self.batch, self.slots, self.bits, self._wire, self.progress)
+            if not (joins or always):
+                return None
+            D.check(D.lib.krk_stream_sync(None))
+            out = self.progress.to_host()
+        else:
+            out = D.peer_round(self.batch, self.slots, self.bits)
+        for t, j in joins.items():
+            for p in j:
+                if out[4][int(self.batch.peer_off[t]) + p] & D.PE_BAD_BITFIELD:
+                    self._refused[t].append(self.peers[t][p])
+                    del self.index[t][self.peers[t][p]]
+                    self.peers[t][p] = None
+                    self.slots.set_live(t, p, False)
+        return out
+
+    def Progress(self):
+        """What the dispatchers derive from the rows, after a peer round over whatever is queued
+        and one synchronise.  One dict a torrent: remaining, complete, endgame; held and wanted by
+        peerID; close and notify, the peerIDs complete() would close and send Complete to; refused,
+        the peers whose join was malformed since the last call.  Pieces queued by ``Arrived`` count
+        once a table round has applied them."""
+        if not self.ds:
+            return []
+        remaining, tflags, held, wanted, status = self._peer_round(always=True)
+        out = []
+        for t, ps in enumerate(self.peers):
+            at = int(self.batch.peer_off[t])
+            named = [(p, peerID) for p, peerID in enumerate(ps) if peerID in self.index[t]]
+            out.append({"remaining": int(remaining[t]), "complete": bool(tflags[t] & D.PE_TORRENT_COMPLETE),
+                        "endgame": bool(tflags[t] & D.PE_ENDGAME),
+                        "held": {peerID: int(held[at + p]) for p, peerID in named},
+                        "wanted": {peerID: int(wanted[at + p]) for p, peerID in named},
+                        "close": [peerID for p, peerID in named if status[at + p] & D.PE_CLOSE],
+                        "notify": [peerID for p, peerID in named if status[at + p] & D.PE_NOTIFY],
+                        "refused": self._refused[t]})
+            self._refused[t] = []
+        return out
+
     def _round(self, out=None, records=None, picks=None):
         """One table round at the dispatchers' clock: the queued events, `records`, the picks."""
         ev, self._events = self._events, {name: {} for name in self._events}
+        for t, gone in ev["gone"].items():  # applied by this round: the slots are free after it
+            for p in gone:
+                self.peers[t][p] = None
         self.table.events(arrived={t: sorted(s) for t, s in ev["arrived"].items()},
                           gone={t: sorted(s) for t, s in ev["gone"].items()}, marks=ev["marks"],
                           holds={t: sorted(s, key=lambda h: h[::-1]) for t, s in ev["holds"].items()}, records=records)
@@ -423,6 +522,7 @@ class RequestTable:
         dups = [self.endgame(t) for t in range(len(self.ds))]
         flags = [d.manager.policy | (D.PR_ALLOW_DUPLICATES if dup else 0) for d, dup in zip(self.ds, dups)]
         self._layout(flags, [d.manager.next_seed() if d.manager.policy == D.PR_SAMPLE else 0 for d in self.ds])
+        self._peer_round()
         if self.gpu:
             self._round()
             D.piece_request_round_dev(self.batch, self.bits, self.out.quota, self.limit, out=self.picks)
@@ -434,7 +534,7 @@ class RequestTable:
             _, picks, n_picked = D.piece_request_round(self.batch, self.bits, quota, self.limit)
             self._round(picks=(picks, n_picked))
         return [{peerID: picks[int(self.batch.peer_off[t]) + p, :int(n_picked[int(self.batch.peer_off[t]) + p])].tolist()
-                 for p, peerID in enumerate(ps)} for t, ps in enumerate(self.peers)]
+                 for p, peerID in enumerate(ps) if peerID is not None} for t, ps in enumerate(self.peers)]
 
     def Resend(self):
         """ResendRound over the resident tables: a table round that leaves the failed list in
@@ -445,6 +545,7 @@ class RequestTable:
             return []
         dups = [self.endgame(t) for t in range(len(self.ds))]
         self._layout([d.manager.policy | (D.PR_ALLOW_DUPLICATES if dup else 0) for d, dup in zip(self.ds, dups)], 0)
+        self._peer_round()
         if self.gpu:
             self._round(out=self.failed)
             D.check(D.lib.krk_stream_sync(None))
