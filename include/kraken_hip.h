@@ -545,6 +545,88 @@ int krk_peer_round_dev(const krk_request_torrent* torrents_host, const krk_peer_
                        uint32_t* remaining_out, uint32_t* torrent_flags_out, uint32_t* held_out, uint32_t* wanted_out,
                        uint32_t* status_out, void* stream);
 
+/* ------------------------------------------- have rounds
+ * The torrent's own row of the resident rows -- `have`, row 0 at bits_off -- loaded from disk,
+ * checked against the blob, persisted and advertised where it lies: restorePieces and
+ * pieceStatusMetadata.Deserialize / Serialize (lib/torrent/storage/agentstorage/pieces.go:63-82,
+ * 130-159), Torrent.Bitfield(), MissingPieces() and BytesDownloaded() (torrent.go:126-140,281-291),
+ * and the bitfield every handshake sends (conn/handshaker.go:286).  A torrent is its
+ * krk_request_torrent, unchanged: only n_pieces and bits_off are read.  Its krk_have_torrent names
+ * what the round does and the spans it reads and writes.  With W = krk_bitfield_words(n_pieces) and
+ * mask = the bits below n_pieces, one round runs in this order:
+ *   1 restore  KRK_HV_RESTORE: sidecar[status_off .. status_off + status_len) is the `_status`
+ *              file, one byte a piece, at any byte offset.  Well formed iff status_len == n_pieces:
+ *              bit i of have becomes (byte i == 1); every byte that is neither 0 nor 1 reads as
+ *              empty and is counted in n_unexpected_out[t] (_dirty = 2 is such a byte).  Otherwise
+ *              flags_out[t] = KRK_HV_BAD_STATUS and the row keeps every bit: a status, never an
+ *              error.  No byte outside the span is read, and none of a malformed span.
+ *              KRK_HV_IN_CACHE: have = mask (pieces.go:144-149).
+ *   2 merge    ok = the W words at ok_bits[ok_off ..], the layout krk_verify_batch_dev and
+ *              krk_piece_bitfield write.  KRK_HV_MERGE_OR (pieces verified this round):
+ *              changed = ok & ~have & mask, have |= ok & mask.  KRK_HV_MERGE_AND (a recheck):
+ *              changed = have & ~ok & mask, have &= ok.  n_changed_out[t] = popcount(changed), and
+ *              changed_out[changed_off ..] the first min(n_changed, changed_cap) changed pieces,
+ *              ascending: under OR exactly the `arrived` list of krk_request_table_round*.
+ *   3 derive   n_complete_out[t] = popcount(have & mask); bytes_out[t] = BytesDownloaded() =
+ *              min(n_complete * piece_length, length), computed without the product (piece_length
+ *              0, or n_complete > length / piece_length, gives length).
+ *     emit     KRK_HV_EMIT_STATUS: n_pieces bytes at status_out[status_out_off ..], byte i = bit i
+ *              (Serialize; dirty is in-memory only and never emitted).
+ *              KRK_HV_EMIT_WIRE: 8 + 8 W bytes at wire_out[wire_out_off ..], MarshalBinary of
+ *              Bitfield() -- the uint64 big-endian n_pieces, then each word big-endian -- the
+ *              byte-exact inverse of what krk_peer_round accepts (bits {0, 9} of 10 =
+ *              00 00 00 00 00 00 00 0A  00 00 00 00 00 00 02 01; no pieces: eight zero bytes).
+ *              KRK_HV_EMIT_MISSING: MissingPieces(): the first min(n_pieces - n_complete,
+ *              missing_cap) clear pieces, ascending, at missing_out[missing_off ..].
+ * A step that wrote the row (a well-formed restore, the cache, a merge) leaves the tail bits of
+ * its last word clear; tail bits of have and of ok on input are ignored.  The blocked rows, the
+ * peers' rows and the table are not touched.  flags_out, n_unexpected_out, n_changed_out,
+ * n_complete_out and bytes_out are stored for every torrent (0 where a step did not run): the
+ * caller pre-zeroes nothing; nothing outside an emitted span or past a list's stored prefix is
+ * written, and the byte spans start at any byte.  KRK_EINVAL, refused before anything is touched:
+ * an unknown flag bit, both flags of an exclusive pair, a non-zero reserved field, a negative
+ * piece_length or length, n_pieces >= 2^32, an offset plus length or cap that overflows, an offset
+ * of 2^48 or more, a NULL array that a set flag reads or writes at least one element of.  The
+ * regions the torrents name in one array must not overlap. */
+#define KRK_HV_RESTORE 0x01u
+#define KRK_HV_IN_CACHE 0x02u      /* exclusive with KRK_HV_RESTORE */
+#define KRK_HV_MERGE_OR 0x04u
+#define KRK_HV_MERGE_AND 0x08u     /* exclusive with KRK_HV_MERGE_OR */
+#define KRK_HV_EMIT_STATUS 0x10u
+#define KRK_HV_EMIT_WIRE 0x20u
+#define KRK_HV_EMIT_MISSING 0x40u
+#define KRK_HV_BAD_STATUS 1u       /* flags_out */
+typedef struct {
+    uint32_t flags;
+    uint32_t reserved;                  /* 0 */
+    int64_t piece_length, length;       /* MetaInfo.PieceLength(), Length() */
+    uint64_t status_off, status_len;    /* bytes in `sidecar` */
+    uint64_t ok_off;                    /* first word in `ok_bits` */
+    uint64_t changed_off, changed_cap;  /* in changed_out */
+    uint64_t missing_off, missing_cap;  /* in missing_out */
+    uint64_t status_out_off;            /* any byte offset in status_out */
+    uint64_t wire_out_off;              /* any byte offset in wire_out */
+} krk_have_torrent;                     /* parallel to torrents[] */
+/* The whole round of n_torrents torrents on the host.  No device. */
+int krk_have_round(const krk_request_torrent* torrents, const krk_have_torrent* haves, uint64_t n_torrents,
+                   uint64_t* bits, const uint8_t* sidecar, const uint64_t* ok_bits, uint32_t* flags_out,
+                   uint32_t* n_unexpected_out, uint32_t* n_changed_out, uint32_t* changed_out,
+                   uint32_t* n_complete_out, uint64_t* bytes_out, uint8_t* status_out, uint8_t* wire_out,
+                   uint32_t* missing_out);
+/* The same on the device (have_round.hip), bit for bit; asynchronous on `stream`: one launch, one
+ * workgroup a torrent.  bits_dev, ok_bits_dev and bytes_out (8-byte aligned), the uint32 outputs
+ * (4-byte aligned) and sidecar_dev, status_out and wire_out (any alignment) are device memory or
+ * page-locked host memory (krk_host_alloc): anything else is KRK_EINVAL before anything is
+ * launched.  torrents_host and haves_host are host memory, copied into the library's staging as
+ * one block before the call returns.  n_torrents == 0 is KRK_OK; KRK_ENODEV without a gfx950
+ * device: there is no fall-back to the host form. */
+int krk_have_round_dev(const krk_request_torrent* torrents_host, const krk_have_torrent* haves_host,
+                       uint64_t n_torrents, uint64_t* bits_dev, const uint8_t* sidecar_dev,
+                       const uint64_t* ok_bits_dev, uint32_t* flags_out, uint32_t* n_unexpected_out,
+                       uint32_t* n_changed_out, uint32_t* changed_out, uint32_t* n_complete_out,
+                       uint64_t* bytes_out, uint8_t* status_out, uint8_t* wire_out, uint32_t* missing_out,
+                       void* stream);
+
 /* ------------------------------------------- announce rounds
  * Whom an announcing peer talks to: the tracker's announce (tracker/trackerserver/announce.go:75-115)
  * for a batch of announces at one clock instant -- peerstore UpdatePeer and GetPeers

@@ -277,6 +277,11 @@ int krk_request_table_geometry(uint64_t* chunk, uint64_t* tile);
  * stride -- and the row words one lane takes in a step (a wave covers 64 times that) -- for the
  * tests that pin krk_peer_round_dev's edges.  No device. */
 int krk_peer_round_geometry(uint64_t* unit_cap, uint64_t* lane_words);
+/* The shape of have_round.hip as built (kernel name "have_round"): the most torrents a launch
+ * gives a workgroup of their own -- beyond it the workgroups stride -- and the row words a
+ * workgroup takes in a pass (one a lane) -- for the tests that pin krk_have_round_dev's edges.
+ * No device. */
+int krk_have_round_geometry(uint64_t* unit_cap, uint64_t* pass_words);
 /* The shape of the SHA-256 host share as built (offload.cpp): the bytes of one device-to-host copy
  * (a chain longer than that comes down in several), the pinned buffers an offload thread's copy
  * ring has (a chain of more chunks than that wraps it) and those of a resumer

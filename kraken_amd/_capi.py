@@ -102,6 +102,13 @@ class krk_peer_join(C.Structure):
     _fields_ = [("peer", C.c_uint32), ("reserved", C.c_uint32), ("wire_off", C.c_uint64), ("wire_len", C.c_uint64)]
 
 
+class krk_have_torrent(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("reserved", C.c_uint32), ("piece_length", C.c_int64), ("length", C.c_int64),
+                ("status_off", C.c_uint64), ("status_len", C.c_uint64), ("ok_off", C.c_uint64), ("changed_off", C.c_uint64),
+                ("changed_cap", C.c_uint64), ("missing_off", C.c_uint64), ("missing_cap", C.c_uint64),
+                ("status_out_off", C.c_uint64), ("wire_out_off", C.c_uint64)]
+
+
 class krk_announce_torrent(C.Structure):
     _fields_ = [("n_peers", C.c_uint64), ("n_windows", C.c_uint32), ("cur_row", C.c_uint32), ("n_origins", C.c_uint32),
                 ("reserved", C.c_uint32), ("bits_off", C.c_uint64)]
@@ -217,6 +224,9 @@ def _load() -> C.CDLL:
         "krk_peer_round_dev": (i, [C.POINTER(krk_request_torrent), C.POINTER(krk_peer_torrent), C.c_uint64, vp, vp, vp, vp,
                                    vp, vp, vp, vp, vp, vp, vp]),
         "krk_peer_round_geometry": (i, [u64p, u64p]),
+        "krk_have_round": (i, [C.POINTER(krk_request_torrent), C.POINTER(krk_have_torrent), C.c_uint64] + [vp] * 12),
+        "krk_have_round_dev": (i, [C.POINTER(krk_request_torrent), C.POINTER(krk_have_torrent), C.c_uint64] + [vp] * 13),
+        "krk_have_round_geometry": (i, [u64p, u64p]),
         "krk_announce_handout": (i, [C.POINTER(krk_announce_torrent), C.c_uint64, u64p, C.POINTER(krk_announce), C.c_uint32,
                                      C.c_uint32, u32p, u32p, u32p]),
         "krk_announce_round": (i, [C.POINTER(krk_announce_torrent), C.c_uint64, u64p, C.POINTER(krk_announce), C.c_uint64,

@@ -12,8 +12,12 @@ received since the last call, and one ``krk_verify_pieces_host`` call checks the
 all on the GPU instead of one ``hash.Hash32`` per piece.  ``Torrent.Recheck``
 re-reads the download file against the metainfo (``krk_verify_files``) and takes
 the resulting Bitfield() as the piece status.  The download-file and piece-status
-machinery around it (CADownloadStore, pieces.go metadata) is out of scope; a plain
-file stands in for it.
+machinery around it (CADownloadStore) is out of scope; a plain file stands in for it.
+
+The piece status is persisted as the reference's ``_status`` sidecar (pieces.go:63-82: one
+byte a piece, 0 empty, 1 complete) beside the download file, written as pieces complete;
+``Torrent(..., restore=True)`` reads it back through ``krk_have_round`` (restorePieces,
+pieces.go:130-159).
 """
 from __future__ import annotations
 
@@ -52,13 +56,47 @@ def verify_pieces(datas, expected) -> np.ndarray:
 class Torrent:
     """agentstorage.Torrent's write path over one download file."""
 
-    def __init__(self, mi: core.MetaInfo, path: str):
+    def __init__(self, mi: core.MetaInfo, path: str, restore: bool = False):
         self.mi = mi
         self.path = path
+        self.status_path = path + "_status"
         self.complete = np.zeros(mi.NumPieces(), dtype=bool)
         if not os.path.exists(path):
             with open(path, "wb") as f:
                 f.truncate(mi.Length())
+        if restore and os.path.exists(self.status_path):
+            self._restore()
+        else:
+            self._write_status()
+
+    def _write_status(self):
+        with open(self.status_path, "wb") as f:
+            f.write(self.complete.astype(np.uint8).tobytes())
+
+    def _restore(self):
+        """restorePieces: the sidecar through krk_have_round; a byte that is neither 0 nor 1 (a
+        piece left dirty by a crash) reads as empty, a sidecar of the wrong length is an error."""
+        from . import device as D
+        with open(self.status_path, "rb") as f:
+            status = f.read()
+        batch = D.RequestBatch([self.NumPieces()], 0)
+        bits = np.zeros(max(batch.total_words, 1), dtype=np.uint64)
+        out = D.have_round(batch, D.HaveBatch(batch).plan(D.HV_RESTORE, {0: status}), bits)
+        if out[0][0] & D.HV_BAD_STATUS:
+            raise ValueError(f"piece status of {len(status)} bytes for {self.NumPieces()} pieces: {self.status_path}")
+        self.complete = D.bitfield_bools(bits, self.NumPieces())
+
+    def Bitfield(self) -> np.ndarray:
+        """torrent.go:130-140: a copy of the piece status, one bool a piece."""
+        return self.complete.copy()
+
+    def MissingPieces(self) -> list:
+        """torrent.go:281-291."""
+        return np.flatnonzero(~self.complete).tolist()
+
+    def BytesDownloaded(self) -> int:
+        """torrent.go:126-128."""
+        return min(int(self.complete.sum()) * self.mi.PieceLength(), self.mi.Length())
 
     def NumPieces(self) -> int:
         return self.mi.NumPieces()
@@ -85,6 +123,9 @@ class Torrent:
             f.seek(self.getFileOffset(pi))
             f.write(memoryview(data))
         self.complete[pi] = True
+        with open(self.status_path, "r+b") as f:
+            f.seek(pi)
+            f.write(b"\x01")
 
     def Recheck(self) -> np.ndarray:
         """The recheck the reference lacks: the download file's pieces against the metainfo's
@@ -94,6 +135,7 @@ class Torrent:
         from . import device as D
         bits, _, _, _ = D.verify_files([self.path], [self.mi.Length()], self.mi.PieceLength(), self.mi.PieceSums())
         self.complete = D.bitfield_bools(bits, self.NumPieces())
+        self._write_status()
         return self.complete
 
     def WritePiece(self, data, pi: int) -> None:

@@ -21,6 +21,17 @@ __device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
     return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
 }
 
+// The aligned dword at a, little-endian, of which only the bytes inside [lo, hi) are read (the
+// others are zero): one load when the span covers it, byte loads at the span's two edges.
+__device__ __forceinline__ uint32_t span_dword(uint64_t a, uint64_t lo, uint64_t hi) {
+    if (a >= lo && a + 4 <= hi) return *as_global<uint32_t>(a);
+    uint32_t x = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < 4; ++k)
+        if (a + k >= lo && a + k < hi) x |= (uint32_t)*as_global<uint8_t>(a + k) << (8 * k);
+    return x;
+}
+
 // Bytes [a, a+n) (n <= 64, any alignment) as 16 little-endian words, zero padded
 // past n.  Only dword-ALIGNED loads are issued, and only for dwords holding at
 // least one requested byte, so nothing outside the run's pages is touched and no

@@ -476,6 +476,35 @@ hipError_t launch_peer_round(const PeTorrent* tors, uint64_t n_tors, uint64_t n_
                              uint32_t* remaining, uint32_t* tflags, uint32_t* held, uint32_t* wanted, uint32_t* status,
                              hipStream_t s);
 
+// One torrent of a have round (have_round.hip, have_round_math.hpp): its `have` row at
+// bits[bits_off ..] and the spans of its krk_have_torrent, each an offset in the caller's array.
+struct alignas(16) HvTorrent {
+    uint64_t n_pieces;  // < 2^32
+    uint64_t bits_off;
+    int64_t piece_length, length;
+    uint64_t status_off, status_len, ok_off;
+    uint64_t changed_off, changed_cap, missing_off, missing_cap;
+    uint64_t status_out_off, wire_out_off;
+    uint32_t flags;  // hv::k*
+    uint32_t pad;
+};
+static_assert(sizeof(HvTorrent) == 112, "HvTorrent layout");
+constexpr uint32_t kHvUnitCap = 4096;   // the torrents a launch gives a workgroup of their own
+constexpr uint32_t kHvPassWords = 256;  // the row words a workgroup takes in a pass: one a lane
+// Arrays the round touches, each nullable when no torrent's flags name it.
+struct HvArrays {
+    uint64_t* bits;
+    const uint8_t* sidecar;
+    const uint64_t* ok;
+    uint32_t *flags_out, *n_unexpected, *n_changed, *changed, *n_complete;
+    uint64_t* bytes;
+    uint8_t *status_out, *wire_out;
+    uint32_t* missing;
+};
+// One workgroup a torrent: the row restored, merged and emitted, every per-torrent output stored.
+// The flags are valid (hv::flags_error).
+hipError_t launch_have_round(const HvTorrent* tors, uint64_t n_tors, const HvArrays& a, hipStream_t s);
+
 // ---------------------------------------------------------------- announce rounds
 // One announce round (announce_round.hip, announce_math.hpp): the update launch sets every
 // announcer's bits in window 0 of its torrent (atomic or), the handout launch -- one wave an

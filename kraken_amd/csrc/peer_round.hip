@@ -46,16 +46,6 @@ __device__ __forceinline__ uint64_t unit_owner(const PeTorrent* __restrict__ tor
     return lo;
 }
 
-// The aligned dword at a, little-endian, of which only the bytes inside [lo, hi) are read (the
-// others are zero): one load when the span covers it, byte loads at the span's two edges.
-__device__ __forceinline__ uint32_t span_dword(uint64_t a, uint64_t lo, uint64_t hi) {
-    if (a >= lo && a + 4 <= hi) return *as_global<uint32_t>(a);
-    uint32_t x = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < 4; ++k)
-        if (a + k >= lo && a + k < hi) x |= (uint32_t)*as_global<uint8_t>(a + k) << (8 * k);
-    return x;
-}
 // The three dwords that hold the eight bytes at `at` (any alignment) ...
 __device__ __forceinline__ void wire_load(uint64_t at, uint64_t lo, uint64_t hi, uint32_t (&d)[3]) {
     const uint64_t a = at & ~uint64_t(3);

@@ -8,7 +8,7 @@ import os
 import numpy as np
 
 from ._capi import (check, krk_blob, krk_file_blob, krk_chunk, krk_launch_rec, krk_nodes, krk_planner_rates,
-                    krk_request_torrent, krk_resend_torrent, krk_failed_request, krk_table_torrent, krk_peer_torrent, krk_announce_torrent, krk_announce, krk_conn_torrent,
+                    krk_request_torrent, krk_resend_torrent, krk_failed_request, krk_table_torrent, krk_peer_torrent, krk_have_torrent, krk_announce_torrent, krk_announce, krk_conn_torrent,
                     krk_conn_lists, krk_conn_transition, krk_conn_incoming, lib)
 
 ALIGN = 256  # every blob starts 256-byte aligned in the arena
@@ -1278,6 +1278,130 @@ def peer_round_geometry():
     """(the units -- rows -- a launch gives a wave of their own, the row words a lane takes in a step)."""
     c, s = C.c_uint64(), C.c_uint64()
     check(lib.krk_peer_round_geometry(C.byref(c), C.byref(s)))
+    return int(c.value), int(s.value)
+
+
+# ------------------------------------------------------------------ have rounds
+HV_RESTORE, HV_IN_CACHE, HV_MERGE_OR, HV_MERGE_AND, HV_EMIT_STATUS, HV_EMIT_WIRE, HV_EMIT_MISSING = 1, 2, 4, 8, 16, 32, 64
+HV_BAD_STATUS = 1
+
+
+class HaveBatch:
+    """What one have round does to the `have` rows of a RequestBatch.  .structs is the
+    krk_have_torrent array parallel to the batch's.  plan() lays a round out: flags a torrent,
+    status {torrent: sidecar bytes} for HV_RESTORE, the caps of the two lists (default: n_pieces).
+    Every span is packed back to back, torrent after torrent, at whatever byte it falls, the first
+    at `skew` = (sidecar, status_out, wire_out) bytes; only a torrent whose flag asks for a span
+    gets one.  Torrent t's verify words are the W words at ok_off[t] (the rows' word counts added
+    up); its lists start at changed_off[t] / missing_off[t]."""
+
+    def __init__(self, batch: RequestBatch, piece_length=0, length=0):
+        k = len(batch)
+        self.batch = batch
+        self.piece_length = np.broadcast_to(np.asarray(piece_length, dtype=np.int64), (k,)).copy()
+        self.length = np.broadcast_to(np.asarray(length, dtype=np.int64), (k,)).copy()
+        self.ok_off = np.zeros(k + 1, dtype=np.uint64)
+        self.ok_off[1:] = np.cumsum(batch.words)
+        self.structs = (krk_have_torrent * max(k, 1))()
+        self.plan(0)
+
+    def __len__(self):
+        return len(self.batch)
+
+    def plan(self, flags, status=None, changed_cap=None, missing_cap=None, skew=(0, 0, 0)):
+        k, status = len(self), status or {}
+        self.flags = np.broadcast_to(np.asarray(flags, dtype=np.uint32), (k,)).copy()
+        n = self.batch.n_pieces.astype(np.int64)
+        caps = [n if c is None else np.broadcast_to(np.asarray(c, dtype=np.int64), (k,)) for c in (changed_cap, missing_cap)]
+        sidecar = bytearray(skew[0])
+        self.changed_off, self.missing_off, self.status_out_off, self.wire_out_off = ([] for _ in range(4))
+        n_changed = n_missing = 0
+        status_out, wire_out = skew[1], skew[2]
+        for t in range(k):
+            f, span = int(self.flags[t]), bytes(status.get(t, b""))
+            merge = bool(f & (HV_MERGE_OR | HV_MERGE_AND))
+            self.structs[t] = krk_have_torrent(f, 0, int(self.piece_length[t]), int(self.length[t]), len(sidecar), len(span),
+                                               int(self.ok_off[t]), n_changed, int(caps[0][t]) if merge else 0, n_missing,
+                                               int(caps[1][t]) if f & HV_EMIT_MISSING else 0, status_out, wire_out)
+            for offs, at in zip((self.changed_off, self.missing_off, self.status_out_off, self.wire_out_off),
+                                (n_changed, n_missing, status_out, wire_out)):
+                offs.append(at)
+            sidecar += span
+            n_changed += int(caps[0][t]) if merge else 0
+            n_missing += int(caps[1][t]) if f & HV_EMIT_MISSING else 0
+            status_out += int(n[t]) if f & HV_EMIT_STATUS else 0
+            wire_out += 8 + 8 * int(self.batch.words[t]) if f & HV_EMIT_WIRE else 0
+        self.sidecar = np.frombuffer(bytes(sidecar), dtype=np.uint8)
+        self.sizes = (k, k, k, n_changed, k, k, status_out, wire_out, n_missing)  # elements of HaveOutputs.NAMES
+        return self
+
+    def status_span(self, status_out: np.ndarray, t: int) -> bytes:
+        return status_out[self.status_out_off[t]:self.status_out_off[t] + int(self.batch.n_pieces[t])].tobytes()
+
+    def wire_span(self, wire_out: np.ndarray, t: int) -> bytes:
+        return wire_out[self.wire_out_off[t]:self.wire_out_off[t] + 8 + 8 * int(self.batch.words[t])].tobytes()
+
+
+class HaveOutputs:
+    """The outputs of have_round_dev for a planned HaveBatch, in device memory or (pinned=True) in
+    page-locked host memory the kernel writes over PCIe: .flags, .n_unexpected, .n_changed,
+    .n_complete (uint32) and .bytes (uint64) a torrent; .changed and .missing (uint32 lists);
+    .status_out and .wire_out (bytes).  `margin` elements follow every buffer's last (tests)."""
+    NAMES = ("flags", "n_unexpected", "n_changed", "changed", "n_complete", "bytes", "status_out", "wire_out", "missing")
+    DTYPES = (np.uint32, np.uint32, np.uint32, np.uint32, np.uint32, np.uint64, np.uint8, np.uint8, np.uint32)
+
+    def __init__(self, have: HaveBatch, pinned: bool = False, margin: int = 0):
+        self.pinned, self.sizes = pinned, tuple(k + margin for k in have.sizes)
+        for name, dt, k in zip(self.NAMES, self.DTYPES, self.sizes):
+            setattr(self, name, PinnedArray((max(k, 1),), dt) if pinned else DeviceBuffer(max(k, 1) * np.dtype(dt).itemsize))
+
+    def fill(self, byte: int):
+        """Every output byte set to `byte` (tests: the call must store exactly what it owns)."""
+        for b in (getattr(self, n) for n in self.NAMES):
+            if self.pinned:
+                b.a.view(np.uint8)[:] = byte
+            else:
+                b.from_host(np.full(b.nbytes, byte, dtype=np.uint8))
+
+    def to_host(self):
+        """The nine buffers, whole, as numpy arrays in NAMES order, once the call's stream has run."""
+        return tuple(b.a[:k].copy() if self.pinned else b.to_host(dt, k)
+                     for b, dt, k in zip((getattr(self, n) for n in self.NAMES), self.DTYPES, self.sizes))
+
+
+def have_round(batch: RequestBatch, have: HaveBatch, bits, ok=None, fill: int = 0, margin: int = 0):
+    """krk_have_round: the whole have round on the host.  bits (uint64, the batch's layout) is
+    updated in place; ok (uint64, have.ok_off's layout) is the verify result of a merge.  Returns
+    HaveOutputs.NAMES as numpy arrays, each whole: `margin` elements longer than the plan and
+    holding the byte `fill` wherever the round stored nothing."""
+    if bits.dtype != np.uint64 or not bits.flags.c_contiguous or not bits.flags.writeable or bits.size < batch.total_words:
+        raise ValueError("have_round: bits is updated in place: a contiguous uint64 array in the batch's layout")
+    out = [np.frombuffer(bytearray([fill]) * (max(k + margin, 1) * np.dtype(dt).itemsize), dtype=dt)
+           for dt, k in zip(HaveOutputs.DTYPES, have.sizes)]
+    ok = None if ok is None else np.ascontiguousarray(ok, dtype=np.uint64)
+    check(lib.krk_have_round(batch.structs, have.structs, len(batch), bits.ctypes.data if bits.size else None,
+                             have.sidecar.ctypes.data if have.sidecar.size else None,
+                             ok.ctypes.data if ok is not None and ok.size else None,
+                             *(a.ctypes.data if k + margin else None for a, k in zip(out, have.sizes))))
+    return tuple(a[:k + margin] for a, k in zip(out, have.sizes))
+
+
+def have_round_dev(batch: RequestBatch, have: HaveBatch, bits_dev, sidecar_dev, ok_dev, out: HaveOutputs, stream=None):
+    """krk_have_round_dev: the have round in one call on the device, asynchronous on `stream`.
+    bits_dev: DeviceBuffer or PinnedArray in the batch's layout, updated where it lies; sidecar_dev:
+    the bytes of have.sidecar, and ok_dev: the verify words (krk_verify_batch_dev's bitfield), each
+    a DeviceBuffer or PinnedArray or None.  Returns out, filled once the stream has run the call."""
+    check(lib.krk_have_round_dev(batch.structs, have.structs, len(batch), bits_dev.ptr,
+                                 sidecar_dev.ptr if sidecar_dev is not None else None,
+                                 ok_dev.ptr if ok_dev is not None else None,
+                                 *(getattr(out, n).ptr if k else None for n, k in zip(out.NAMES, out.sizes)), stream))
+    return out
+
+
+def have_round_geometry():
+    """(the torrents a launch gives a workgroup of their own, the row words a workgroup takes in a pass)."""
+    c, s = C.c_uint64(), C.c_uint64()
+    check(lib.krk_have_round_geometry(C.byref(c), C.byref(s)))
     return int(c.value), int(s.value)
 
 

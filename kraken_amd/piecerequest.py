@@ -347,7 +347,12 @@ class RequestTable:
     torrent's layout has `spare_peers` empty slots after its peers, ``AddPeer`` queues a join from
     the handshake's wire bytes into the lowest free slot, ``PeerComplete`` queues a Complete
     message, and ``Progress`` reads what the dispatcher derives from the rows.  A removed peer's
-    slot is free again once a round has applied the removal."""
+    slot is free again once a round has applied the removal.
+
+    The torrents' own rows are loaded, checked, persisted and advertised where they lie
+    (``krk_have_round`` / ``krk_have_round_dev``): ``Restore``, ``Verified``, ``Handshake``,
+    ``Status`` and ``MissingPieces`` each run one have round at once; ``self.have``, the host's
+    mirror, follows from the round's changed list or emitted status."""
 
     def __init__(self, dispatchers, placement: str = "host", cap: int = D.RT_MAX_ENTRIES, spare_peers: int = 0):
         if placement not in ("host", "gpu"):
@@ -438,6 +443,74 @@ class RequestTable:
     def endgame(self, t: int) -> bool:
         d = self.ds[t]
         return not d.disable_endgame and d.n_pieces - int(self.have[t].sum()) <= d.endgame_threshold
+
+    # -- the torrents' own rows: restored, checked, persisted and advertised where they lie
+    def _have_round(self, flags, status=None, ok=None):
+        """One have round (``krk_have_round`` / ``krk_have_round_dev``) now, and one synchronise:
+        (the HaveBatch, its outputs by name as numpy arrays)."""
+        have = D.HaveBatch(self.batch, [getattr(d, "piece_length", 0) for d in self.ds], [getattr(d, "length", 0) for d in self.ds])
+        have.plan(flags, status)
+        if self.gpu:
+            side = None
+            if have.sidecar.size:
+                side = D.DeviceBuffer(have.sidecar.nbytes)
+                side.from_host(have.sidecar)
+            out = D.have_round_dev(self.batch, have, self.bits, side, ok, D.HaveOutputs(have, pinned=True))
+            D.check(D.lib.krk_stream_sync(None))
+            out = out.to_host()
+        else:
+            out = D.have_round(self.batch, have, self.bits, ok)
+        return have, dict(zip(D.HaveOutputs.NAMES, out))
+
+    def _every(self, flags):
+        return [flags] * len(self.ds)
+
+    def Restore(self, t: int, status_bytes=None, in_cache: bool = False):
+        """restorePieces for torrent t: its row from the `_status` sidecar's bytes (one a piece), or
+        every piece set for a torrent found in the cache.  Returns {"bad_status", "unexpected",
+        "complete", "bytes"}; a sidecar of the wrong length is bad_status and changes nothing."""
+        if (status_bytes is None) == (not in_cache):
+            raise ValueError("Restore: either the sidecar's bytes or in_cache")
+        flags = [0] * len(self.ds)
+        flags[t] = D.HV_EMIT_STATUS | (D.HV_IN_CACHE if in_cache else D.HV_RESTORE)
+        have, o = self._have_round(flags, None if in_cache else {t: status_bytes})
+        self.have[t][:] = np.frombuffer(have.status_span(o["status_out"], t), dtype=np.uint8).astype(bool)
+        return {"bad_status": bool(o["flags"][t] & D.HV_BAD_STATUS), "unexpected": int(o["n_unexpected"][t]),
+                "complete": int(o["n_complete"][t]), "bytes": int(o["bytes"][t])}
+
+    def Verified(self, ok, mode: str = "or"):
+        """A verify result folded into every torrent's row where it lies.  ok: the bitfields
+        ``krk_verify_batch_dev`` leaves in device memory (placement "gpu": a DeviceBuffer) or their
+        uint64 words ("host"), torrent t's words from the sum of the word counts before it.  mode
+        "or": the set pieces have arrived (their requests are cleared by the next table round);
+        "and": a recheck, the pieces it does not confirm are lost.  Returns the changed pieces a
+        torrent."""
+        if mode not in ("or", "and"):
+            raise ValueError(f"Verified: mode {mode!r} is neither \"or\" nor \"and\"")
+        have, o = self._have_round(self._every(D.HV_MERGE_OR if mode == "or" else D.HV_MERGE_AND), ok=ok)
+        out = []
+        for t in range(len(self.ds)):
+            out.append(o["changed"][have.changed_off[t]:have.changed_off[t] + int(o["n_changed"][t])].tolist())
+            self.have[t][out[t]] = mode == "or"
+            if mode == "or" and out[t]:
+                self._events["arrived"].setdefault(t, set()).update(out[t])
+        return out
+
+    def Handshake(self):
+        """info.Bitfield() as every handshake sends it: the wire bytes a torrent (``AddPeer``'s form)."""
+        have, o = self._have_round(self._every(D.HV_EMIT_WIRE))
+        return [have.wire_span(o["wire_out"], t) for t in range(len(self.ds))]
+
+    def Status(self):
+        """pieceStatusMetadata.Serialize: the `_status` sidecar's bytes a torrent."""
+        have, o = self._have_round(self._every(D.HV_EMIT_STATUS))
+        return [have.status_span(o["status_out"], t) for t in range(len(self.ds))]
+
+    def MissingPieces(self):
+        """Torrent.MissingPieces(): the pieces not yet held, ascending, a torrent."""
+        have, o = self._have_round(self._every(D.HV_EMIT_MISSING))
+        return [o["missing"][have.missing_off[t]:have.missing_off[t] + d.n_pieces - int(o["n_complete"][t])].tolist()
+                for t, d in enumerate(self.ds)]
 
     # -- rounds
     def _peer_round(self, always=False):
