@@ -627,6 +627,91 @@ int krk_have_round_dev(const krk_request_torrent* torrents_host, const krk_have_
                        uint64_t* bytes_out, uint8_t* status_out, uint8_t* wire_out, uint32_t* missing_out,
                        void* stream);
 
+/* ------------------------------------------- serve rounds
+ * The upload side of the resident rows: Dispatcher.handlePieceRequest
+ * (lib/torrent/scheduler/dispatch/dispatcher.go:504-530) for every PieceRequestMessage queued for
+ * a torrent, in arrival order.  A torrent is its krk_request_torrent, unchanged: only n_pieces,
+ * n_peers, bits_off and peer_off are read, and n_peers counts peer SLOTS, as in peer rounds.  Its
+ * krk_serve_torrent names the blob's length and piece_length (MetaInfo.Length(), PieceLength();
+ * n_pieces == krk_num_pieces(length, piece_length) or the call is refused), its live row (the
+ * layout of krk_peer_torrent.live_off) and its requests, requests[req_off .. req_off + n_reqs),
+ * n_reqs <= KRK_SV_MAX_REQUESTS.  A krk_serve_request carries the wire's three int32 fields as
+ * they came, and `peer`, the slot it arrived on.  With plen(i) = MetaInfo.GetPieceLength(i)
+ * (core/metainfo.go:109-118: 0 outside [0, n_pieces), length - piece_length * i for the last
+ * piece, piece_length otherwise), request r takes the FIRST status that applies:
+ *   KRK_SV_CHUNK       offset != 0 or (int64)length != plen(index) (isFullPiece, :500-502; "reading
+ *                      / writing chunk of piece not supported").  A piece of 2^31 bytes or more can
+ *                      therefore never be served, as in the reference.
+ *   KRK_SV_INDEX       index < 0 or index >= n_pieces -- reached only with offset == length == 0
+ *                      (Torrent.GetPieceReader's "invalid piece index", agentstorage/torrent.go:260-269).
+ *   KRK_SV_INCOMPLETE  bit index of have is clear ("piece not complete").
+ *   KRK_SV_GONE        the slot's live bit is clear: the send fails, nothing is touched, no bit set.
+ *   KRK_SV_OK          the piece is sent.
+ * Stored for every request, at req_off + r: status_out; file_off_out = piece_length * index
+ * (getFileOffset, :293-295); len_out = length; send_off_out = the sum of len_out over the torrent's
+ * OK requests before r -- the payloads lie end to end in one send buffer at these offsets; and,
+ * when token_size > 0, token_off_out = the same running sum over max(len * 8 / token_size, 1), the
+ * egress tokens Conn.sendPiecePayload reserves (conn/conn.go:254-261,
+ * utils/bandwidth/limiter.go:100-117).  The offsets, the length and the token term are 0 for a
+ * request that is not OK.  The limiter's float bucket, its clock and its sleep stay with the
+ * caller: the call delivers the integer token counts and their order.
+ * Stored for every slot, at peer_off + p: n_received_out (its requests, whatever their status:
+ * incrementPieceRequestsReceived) and n_sent_out (its OK requests: incrementPiecesSent).  Where
+ * n_sent > 0, sent[peer_off + p] = now (touchLastPieceSent): `sent` is the resident LastPieceSent
+ * array krk_conn_preempt* reads; its other elements are left alone.
+ * Stored for every torrent: n_ok_out, bytes_out and (token_size > 0) tokens_out, the totals.
+ * Rows: bit index of bits_p is set for every OK request ("Assume that the peer successfully
+ * received the piece"); a repeated request is served again, as the reference serves it.  No other
+ * word of bits changes.
+ * Two deliberate differences from the reference.  For a negative index it would index out of range
+ * and panic; here that is KRK_SV_CHUNK or KRK_SV_INDEX.  It does not bump numPeersByPiece when it
+ * sets the peer's bit; in this library the counts are the rows' column sum at all times, so a later
+ * request round counts the bit.
+ *
+ * token_off_out and tokens_out are nullable, and not written, when token_size == 0.  KRK_EINVAL,
+ * refused before anything is touched: a request's peer >= n_peers, n_reqs above the maximum, more
+ * than 2^30 slots, a negative length, n_pieces != krk_num_pieces(length, piece_length), a
+ * piece_length <= 0 ("piece length must be positive"), a non-zero reserved field, now < 0,
+ * requests adding up to 2^32 or more, an offset of 2^48 or more, a NULL that is not nullable (bits
+ * with no words, live and the per-slot arrays with no slots, requests and the per-request outputs
+ * with no requests are).  The regions the torrents name in one array must not overlap. */
+#define KRK_SV_MAX_REQUESTS 4096u
+#define KRK_SV_OK 0u
+#define KRK_SV_CHUNK 1u
+#define KRK_SV_INDEX 2u
+#define KRK_SV_INCOMPLETE 3u
+#define KRK_SV_GONE 4u
+typedef struct {
+    uint32_t peer;                  /* the slot the message arrived on */
+    int32_t index, offset, length;  /* PieceRequestMessage, as on the wire */
+} krk_serve_request;
+typedef struct {
+    int64_t length, piece_length;   /* MetaInfo.Length(), PieceLength() */
+    uint64_t live_off;              /* first word of its live row in `live` */
+    uint64_t req_off;               /* first request in `requests` and in the per-request outputs */
+    uint32_t n_reqs;                /* <= KRK_SV_MAX_REQUESTS */
+    uint32_t reserved;              /* 0 */
+} krk_serve_torrent;                /* parallel to torrents[] */
+/* The whole round of n_torrents torrents on the host.  No device. */
+int krk_serve_round(const krk_request_torrent* torrents, const krk_serve_torrent* serves, uint64_t n_torrents,
+                    uint64_t* bits, const uint64_t* live, const krk_serve_request* requests, int64_t now,
+                    uint64_t token_size, uint32_t* status_out, int64_t* file_off_out, uint32_t* len_out,
+                    uint64_t* send_off_out, uint64_t* token_off_out, uint32_t* n_received_out, uint32_t* n_sent_out,
+                    int64_t* sent, uint32_t* n_ok_out, uint64_t* bytes_out, uint64_t* tokens_out);
+/* The same on the device (serve_round.hip), bit for bit; asynchronous on `stream`: one launch, one
+ * workgroup a torrent.  bits_dev, sent_dev and the outputs are device memory or page-locked host
+ * memory (krk_host_alloc), the 64-bit arrays 8-byte and the others 4-byte aligned: anything else is
+ * KRK_EINVAL before anything is launched.  torrents_host, serves_host, live_host and requests_host
+ * are host memory: the requests are checked as above, and all four are copied into the library's
+ * staging as one block, before the call returns.  n_torrents == 0 is KRK_OK; KRK_ENODEV without a
+ * gfx950 device: there is no fall-back to the host form. */
+int krk_serve_round_dev(const krk_request_torrent* torrents_host, const krk_serve_torrent* serves_host,
+                        uint64_t n_torrents, uint64_t* bits_dev, const uint64_t* live_host,
+                        const krk_serve_request* requests_host, int64_t now, uint64_t token_size, uint32_t* status_out,
+                        int64_t* file_off_out, uint32_t* len_out, uint64_t* send_off_out, uint64_t* token_off_out,
+                        uint32_t* n_received_out, uint32_t* n_sent_out, int64_t* sent_dev, uint32_t* n_ok_out,
+                        uint64_t* bytes_out, uint64_t* tokens_out, void* stream);
+
 /* ------------------------------------------- announce rounds
  * Whom an announcing peer talks to: the tracker's announce (tracker/trackerserver/announce.go:75-115)
  * for a batch of announces at one clock instant -- peerstore UpdatePeer and GetPeers

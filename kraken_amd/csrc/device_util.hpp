@@ -32,6 +32,32 @@ __device__ __forceinline__ uint32_t span_dword(uint64_t a, uint64_t lo, uint64_t
     return x;
 }
 
+// keys[0, n2) in LDS ascending, n2 a power of two, by a workgroup of kBlock threads: a bitonic
+// network, a barrier a stage (and one before the first: the keys were just written).
+template <uint32_t kBlock>
+__device__ inline void sort_keys(uint64_t* keys, uint32_t n2, uint32_t tid) {
+    __syncthreads();
+    for (uint32_t k = 2; k <= n2; k <<= 1)
+        for (uint32_t j = k >> 1; j; j >>= 1) {
+            for (uint32_t t = tid; t < n2 / 2; t += kBlock) {
+                const uint32_t i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), q = i | j;
+                const uint64_t a = keys[i], b = keys[q];
+                if ((a > b) == !(i & k)) keys[i] = b, keys[q] = a;
+            }
+            __syncthreads();
+        }
+}
+// The first index of keys[0, n) (ascending) whose key is not below x.
+__device__ inline uint32_t lower_bound(const uint64_t* keys, uint32_t n, uint64_t x) {
+    uint32_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (keys[mid] < x) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
 // Bytes [a, a+n) (n <= 64, any alignment) as 16 little-endian words, zero padded
 // past n.  Only dword-ALIGNED loads are issued, and only for dwords holding at
 // least one requested byte, so nothing outside the run's pages is touched and no

@@ -505,6 +505,44 @@ struct HvArrays {
 // The flags are valid (hv::flags_error).
 hipError_t launch_have_round(const HvTorrent* tors, uint64_t n_tors, const HvArrays& a, hipStream_t s);
 
+// One torrent of a serve round (serve_round.hip, serve_round_math.hpp): its rows as a request
+// round's, its per-slot outputs from peer_off, its per-request outputs from req_off, and its staged
+// requests (sv::Request) and live words (uint64) from req_at / live_at.
+namespace sv {
+struct Request;
+}
+struct alignas(16) SvTorrent {
+    uint64_t n_pieces;  // < 2^32
+    uint64_t bits_off;
+    uint64_t peer_off;
+    uint64_t req_off;
+    int64_t length, piece_length;
+    uint64_t req_at, live_at;
+    uint32_t n_peers;  // <= 2^30
+    uint32_t n_reqs;   // <= kSvTile
+    uint64_t pad;
+};
+static_assert(sizeof(SvTorrent) == 80, "SvTorrent layout");
+constexpr uint32_t kSvChunk = 256;  // the requests one step of the classify-and-scan takes: one a thread
+constexpr uint32_t kSvTile = 4096;  // KRK_SV_MAX_REQUESTS: the keys one workgroup sorts in LDS
+// The arrays a serve round touches; token_off and tokens are read only when token_size > 0.
+struct SvArrays {
+    uint64_t* bits;
+    uint32_t* status;
+    int64_t* file_off;
+    uint32_t* len;
+    uint64_t *send_off, *token_off;
+    uint32_t *n_received, *n_sent;
+    int64_t* sent;
+    uint32_t* n_ok;
+    uint64_t *bytes, *tokens;
+};
+// One workgroup a torrent: every per-request, per-slot and per-torrent output stored, bit `index`
+// of bits_p set for every served request, sent[peer_off + p] = now where something was sent.  The
+// requests are valid (every peer < n_peers).
+hipError_t launch_serve_round(const SvTorrent* tors, uint64_t n_tors, const sv::Request* reqs, const uint64_t* live,
+                              int64_t now, uint64_t token_size, const SvArrays& a, hipStream_t s);
+
 // ---------------------------------------------------------------- announce rounds
 // One announce round (announce_round.hip, announce_math.hpp): the update launch sets every
 // announcer's bits in window 0 of its torrent (atomic or), the handout launch -- one wave an

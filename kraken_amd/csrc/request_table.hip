@@ -62,32 +62,6 @@ __device__ inline uint32_t block_rank(bool f, uint32_t (&wsum)[2][kWaves], uint3
     return before + (uint32_t)__popcll(bal & ((1ull << lane) - 1));
 }
 
-// keys[0, n2) ascending, n2 a power of two: a bitonic network, a barrier a stage (and one before
-// the first: the keys were just written).
-__device__ inline void sort_keys(uint64_t* keys, uint32_t n2, uint32_t tid) {
-    __syncthreads();
-    for (uint32_t k = 2; k <= n2; k <<= 1)
-        for (uint32_t j = k >> 1; j; j >>= 1) {
-            for (uint32_t t = tid; t < n2 / 2; t += kBlock) {
-                const uint32_t i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), q = i | j;
-                const uint64_t a = keys[i], b = keys[q];
-                if ((a > b) == !(i & k)) keys[i] = b, keys[q] = a;
-            }
-            __syncthreads();
-        }
-}
-
-// The first index of keys[0, n) (ascending) whose key is not below x.
-__device__ inline uint32_t lower_bound(const uint64_t* keys, uint32_t n, uint64_t x) {
-    uint32_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (keys[mid] < x) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
 __global__ void __launch_bounds__(kBlock)
 request_table_kernel(const RtTorrent* __restrict__ tors, const uint32_t* __restrict__ arrived_all,
                      const uint32_t* __restrict__ gone_all, const rs::Failed* __restrict__ marks_all,
@@ -205,7 +179,7 @@ request_table_kernel(const RtTorrent* __restrict__ tors, const uint32_t* __restr
         }
         keys[e] = key;
     }
-    sort_keys(keys, n2, tid);
+    sort_keys<kBlock>(keys, n2, tid);
     int32_t* quota = quota_all + T.peer_off;
     for (uint64_t p = tid; p < P; p += kBlock) {
         const uint32_t cnt = lower_bound(keys, n2, (p + 1) << 32) - lower_bound(keys, n2, p << 32);
@@ -248,7 +222,7 @@ request_table_kernel(const RtTorrent* __restrict__ tors, const uint32_t* __restr
         }
         keys[e] = key;
     }
-    sort_keys(keys, n2, tid);
+    sort_keys<kBlock>(keys, n2, tid);
     if (!dup) {
         for (uint32_t e = tid; e < E; e += kBlock) {
             const uint64_t key = keys[e], wi = key >> 38;

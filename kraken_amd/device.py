@@ -8,7 +8,7 @@ import os
 import numpy as np
 
 from ._capi import (check, krk_blob, krk_file_blob, krk_chunk, krk_launch_rec, krk_nodes, krk_planner_rates,
-                    krk_request_torrent, krk_resend_torrent, krk_failed_request, krk_table_torrent, krk_peer_torrent, krk_have_torrent, krk_announce_torrent, krk_announce, krk_conn_torrent,
+                    krk_request_torrent, krk_resend_torrent, krk_failed_request, krk_table_torrent, krk_peer_torrent, krk_have_torrent, krk_serve_torrent, krk_announce_torrent, krk_announce, krk_conn_torrent,
                     krk_conn_lists, krk_conn_transition, krk_conn_incoming, lib)
 
 ALIGN = 256  # every blob starts 256-byte aligned in the arena
@@ -1403,6 +1403,119 @@ def have_round_geometry():
     c, s = C.c_uint64(), C.c_uint64()
     check(lib.krk_have_round_geometry(C.byref(c), C.byref(s)))
     return int(c.value), int(s.value)
+
+
+# ------------------------------------------------------------------ serve rounds
+SV_MAX_REQUESTS = 4096
+SV_OK, SV_CHUNK, SV_INDEX, SV_INCOMPLETE, SV_GONE = 0, 1, 2, 3, 4
+SV_REQUEST = np.dtype([("peer", "<u4"), ("index", "<i4"), ("offset", "<i4"), ("length", "<i4")])
+
+
+class ServeBatch:
+    """The piece requests one serve round answers over a RequestBatch.  .structs is the
+    krk_serve_torrent array parallel to the batch's: the torrents' length and piece_length, their
+    live rows (`live_off`: a PeerBatch's layout) and their request lists.  plan() packs a round's
+    requests {torrent: [(slot, index, offset, length)]}, each list in arrival order, back to back
+    into .requests (SV_REQUEST); torrent t's requests, and its per-request outputs, start at
+    .req_off[t]."""
+
+    def __init__(self, batch: RequestBatch, length, piece_length, live_off):
+        k = len(batch)
+        self.batch = batch
+        self.length = np.broadcast_to(np.asarray(length, dtype=np.int64), (k,)).copy()
+        self.piece_length = np.broadcast_to(np.asarray(piece_length, dtype=np.int64), (k,)).copy()
+        self.live_off = np.asarray(live_off, dtype=np.uint64)
+        self.structs = (krk_serve_torrent * max(k, 1))()
+        self.plan()
+
+    def __len__(self):
+        return len(self.batch)
+
+    def plan(self, requests=None):
+        requests = requests or {}
+        rows, self.req_off = [], []
+        for t in range(len(self)):
+            mine = list(requests.get(t, ()))
+            self.req_off.append(len(rows))
+            self.structs[t] = krk_serve_torrent(int(self.length[t]), int(self.piece_length[t]), int(self.live_off[t]),
+                                                len(rows), len(mine), 0)
+            rows.extend(mine)
+        self.requests = np.array(rows, dtype=SV_REQUEST)
+        k, r, p = len(self), len(rows), self.batch.total_peers
+        self.sizes = (r, r, r, r, r, p, p, k, k, k)  # elements of ServeOutputs.NAMES
+        return self
+
+
+class ServeOutputs:
+    """The outputs of serve_round_dev for a planned ServeBatch, in device memory or (pinned=True)
+    in page-locked host memory the kernel writes over PCIe: .status, .file_off, .len, .send_off and
+    .token_off a request; .n_received and .n_sent a peer slot; .n_ok, .bytes and .tokens a torrent.
+    `margin` elements follow every buffer's last (tests)."""
+    NAMES = ("status", "file_off", "len", "send_off", "token_off", "n_received", "n_sent", "n_ok", "bytes", "tokens")
+    DTYPES = (np.uint32, np.int64, np.uint32, np.uint64, np.uint64, np.uint32, np.uint32, np.uint32, np.uint64, np.uint64)
+
+    def __init__(self, serve: ServeBatch, pinned: bool = False, margin: int = 0):
+        self.pinned, self.sizes = pinned, tuple(k + margin for k in serve.sizes)
+        for name, dt, k in zip(self.NAMES, self.DTYPES, self.sizes):
+            setattr(self, name, PinnedArray((max(k, 1),), dt) if pinned else DeviceBuffer(max(k, 1) * np.dtype(dt).itemsize))
+
+    def fill(self, byte: int):
+        """Every output byte set to `byte` (tests: the call must store exactly what it owns)."""
+        for b in (getattr(self, n) for n in self.NAMES):
+            if self.pinned:
+                b.a.view(np.uint8)[:] = byte
+            else:
+                b.from_host(np.full(b.nbytes, byte, dtype=np.uint8))
+
+    def to_host(self):
+        """The ten buffers, whole, as numpy arrays in NAMES order, once the call's stream has run."""
+        return tuple(b.a[:k].copy() if self.pinned else b.to_host(dt, k)
+                     for b, dt, k in zip((getattr(self, n) for n in self.NAMES), self.DTYPES, self.sizes))
+
+
+def _serve_args(out, sent_ptr):
+    """The eleven output pointers of a serve call: NAMES with `sent` behind n_sent."""
+    return out[:7] + [sent_ptr] + out[7:]
+
+
+def serve_round(batch: RequestBatch, serve: ServeBatch, bits, live, sent, now: int, token_size: int = 0, fill: int = 0,
+                margin: int = 0):
+    """krk_serve_round: the whole serve round on the host.  bits (uint64, the batch's layout) and
+    sent (int64 a peer slot, the LastPieceSent array) are updated in place; live: a PeerBatch's
+    live words.  Returns ServeOutputs.NAMES as numpy arrays, each whole: `margin` elements longer
+    than the plan and holding the byte `fill` wherever the round stored nothing."""
+    for a, t in ((bits, np.uint64), (sent, np.int64)):
+        if a.dtype != t or not a.flags.c_contiguous or not a.flags.writeable:
+            raise ValueError(f"serve_round: bits and sent are updated in place: a contiguous {t} array each")
+    if bits.size < batch.total_words or sent.size < batch.total_peers:
+        raise ValueError("serve_round: bits or sent shorter than the batch's layout")
+    out = [np.frombuffer(bytearray([fill]) * (max(k + margin, 1) * np.dtype(dt).itemsize), dtype=dt)
+           for dt, k in zip(ServeOutputs.DTYPES, serve.sizes)]
+    live = np.ascontiguousarray(live, dtype=np.uint64)
+    ptr = lambda a: a.ctypes.data if a.size else None  # noqa: E731
+    check(lib.krk_serve_round(batch.structs, serve.structs, len(batch), ptr(bits), ptr(live), ptr(serve.requests), int(now),
+                              int(token_size), *_serve_args([a.ctypes.data for a in out], ptr(sent))))
+    return tuple(a[:k + margin] for a, k in zip(out, serve.sizes))
+
+
+def serve_round_dev(batch: RequestBatch, serve: ServeBatch, bits_dev, live, sent_dev, now: int, out: ServeOutputs,
+                    token_size: int = 0, stream=None):
+    """krk_serve_round_dev: the serve round in one call on the device, asynchronous on `stream`.
+    bits_dev and sent_dev: DeviceBuffer or PinnedArray in the batch's layout, updated where they
+    lie; live: a PeerBatch's live words (host).  Returns out, filled once the stream has run the call."""
+    live = np.ascontiguousarray(live, dtype=np.uint64)
+    check(lib.krk_serve_round_dev(batch.structs, serve.structs, len(batch), bits_dev.ptr, live.ctypes.data if live.size else None,
+                                  serve.requests.ctypes.data if serve.requests.size else None, int(now), int(token_size),
+                                  *_serve_args([getattr(out, n).ptr for n in out.NAMES], sent_dev.ptr), stream))
+    return out
+
+
+def serve_round_geometry():
+    """(the requests one step of the classify-and-scan takes, the keys one workgroup sorts in LDS:
+    the most requests a torrent brings to a round)."""
+    c, t = C.c_uint64(), C.c_uint64()
+    check(lib.krk_serve_round_geometry(C.byref(c), C.byref(t)))
+    return int(c.value), int(t.value)
 
 
 AN_MAX_WINDOWS, AN_MAX_ORIGINS, AN_MAX_LIMIT = 8, 8, 64

@@ -352,7 +352,11 @@ class RequestTable:
     The torrents' own rows are loaded, checked, persisted and advertised where they lie
     (``krk_have_round`` / ``krk_have_round_dev``): ``Restore``, ``Verified``, ``Handshake``,
     ``Status`` and ``MissingPieces`` each run one have round at once; ``self.have``, the host's
-    mirror, follows from the round's changed list or emitted status."""
+    mirror, follows from the round's changed list or emitted status.
+
+    The upload side runs on the same rows (``krk_serve_round`` / ``krk_serve_round_dev``):
+    ``Requested`` queues a peer's PieceRequestMessage, ``Serve`` answers everything queued in one
+    round, and ``LastPieceSent`` reads the resident array the round keeps."""
 
     def __init__(self, dispatchers, placement: str = "host", cap: int = D.RT_MAX_ENTRIES, spare_peers: int = 0):
         if placement not in ("host", "gpu"):
@@ -393,6 +397,14 @@ class RequestTable:
         if self.gpu:
             self.progress = D.PeerOutputs(self.batch, pinned=True)  # read after one synchronise
             self._wire = D.DeviceBuffer(1 << 12)
+        self._requests = [[] for _ in self.ds]  # (slot, peerID, index, offset, length), in arrival order
+        self._serve, self._serve_out = None, None  # the ServeBatch, and on "gpu" its page-locked outputs, kept between rounds
+        sent = np.zeros(max(self.batch.total_peers, 1), dtype=np.int64)  # LastPieceSent a slot, 0: never
+        if self.gpu:
+            self.sent = D.DeviceBuffer(sent.nbytes)
+            self.sent.from_host(sent)
+        else:
+            self.sent = sent
 
     def _layout(self, flags, seeds):
         self.batch = D.RequestBatch([d.n_pieces for d in self.ds], [len(ps) for ps in self.peers], flags, seeds)
@@ -512,6 +524,77 @@ class RequestTable:
         return [o["missing"][have.missing_off[t]:have.missing_off[t] + d.n_pieces - int(o["n_complete"][t])].tolist()
                 for t, d in enumerate(self.ds)]
 
+    # -- the upload side: the peers' piece requests answered on the resident rows
+    def Requested(self, t: int, peerID, index: int, offset: int, length: int):
+        """The peer's PieceRequestMessage (handlePieceRequest), queued in arrival order for the next
+        ``Serve``.  The peer may be removed before then: its send fails and nothing is touched."""
+        self._requests[t].append((self.index[t][peerID], peerID, int(index), int(offset), int(length)))
+
+    def LastPieceSent(self, t: int, peerID) -> int:
+        """The clock reading of the peer's last served piece, 0 for none: the resident array."""
+        p = self.index[t][peerID]
+        if p in self._joins.get(t, {}):  # joined since the last round: the slot's element is the peer before it
+            return 0
+        at = int(self.batch.peer_off[t]) + p
+        return int(self.sent.to_host(np.int64, 1, offset=8 * at)[0] if self.gpu else self.sent[at])
+
+    def Serve(self, token_size: int = 0):
+        """One serve round over everything ``Requested`` queued, at the managers' clock, and one
+        synchronise -- two on "gpu" when joins are queued: the peer round that applies them first
+        reads their statuses back.  One dict a torrent: "sends", (peerID, piece, file_off, length,
+        send_off) in arrival order -- the payloads lie end to end at send_off; "refusals", (peerID,
+        index, error) with the reference's error texts; "gone", (peerID, index) in arrival order, the
+        requests whose peer has left -- among them those whose slot another peer has taken since,
+        which never enter the round and are in no count; "bytes" and "tokens", the totals (tokens:
+        max(length * 8 // token_size, 1) a send, 0 when token_size is 0)."""
+        if not self.ds:
+            return []
+        queued, self._requests = self._requests, [[] for _ in self.ds]
+        for t, d in enumerate(self.ds):
+            if queued[t] and not (hasattr(d, "length") and hasattr(d, "piece_length")):
+                raise ValueError(f"Serve: torrent {t} has queued requests and no length / piece_length")
+        self._peer_round()
+        # A torrent without the attributes takes no request: any consistent pair will do.
+        shape = [(getattr(d, "length", d.n_pieces), getattr(d, "piece_length", 1)) for d in self.ds]
+        if self._serve is None or shape != list(zip(self._serve.length.tolist(), self._serve.piece_length.tolist())):
+            self._serve = D.ServeBatch(self.batch, [s[0] for s in shape], [s[1] for s in shape], self.slots.live_off[:-1])
+        serve = self._serve.plan({t: [(p, i, off, ln) for p, peerID, i, off, ln in qs if self.peers[t][p] == peerID]
+                                  for t, qs in enumerate(queued) if qs})
+        clocks = {d.manager.clock.Now() for d in self.ds}
+        if len(clocks) != 1:
+            raise ValueError("RequestTable: the dispatchers of a round share one clock reading")
+        now = clocks.pop()
+        if self.gpu:
+            if self._serve_out is None or self._serve_out.sizes[0] < serve.sizes[0]:  # grown on demand, as _wire
+                self._serve_out = D.ServeOutputs(serve, pinned=True, margin=serve.sizes[0])
+            D.serve_round_dev(self.batch, serve, self.bits, self.slots.live, self.sent, now, self._serve_out, token_size)
+            D.check(D.lib.krk_stream_sync(None))
+            out = [getattr(self._serve_out, n).a for n in D.ServeOutputs.NAMES]
+        else:
+            out = D.serve_round(self.batch, serve, self.bits, self.slots.live, self.sent, now, token_size)
+        o = {n: a.tolist() for n, a in zip(D.ServeOutputs.NAMES, out) if n in ("status", "file_off", "len", "send_off")}
+        errors = {D.SV_CHUNK: lambda i, n: "reading / writing chunk of piece not supported",
+                  D.SV_INDEX: lambda i, n: f"invalid piece index {i}: num pieces = {n}",
+                  D.SV_INCOMPLETE: lambda i, n: "piece not complete"}
+        res = []
+        for t, qs in enumerate(queued):
+            got = {"sends": [], "refusals": [], "gone": [], "bytes": int(out[8][t]), "tokens": int(out[9][t]) if token_size else 0}
+            r = serve.req_off[t]
+            for p, peerID, index, _, _ in qs:
+                if self.peers[t][p] != peerID:  # the slot is another peer's by now: this one has left
+                    got["gone"].append((peerID, index))
+                    continue
+                st = o["status"][r]
+                if st == D.SV_OK:
+                    got["sends"].append((peerID, index, o["file_off"][r], o["len"][r], o["send_off"][r]))
+                elif st == D.SV_GONE:
+                    got["gone"].append((peerID, index))
+                else:
+                    got["refusals"].append((peerID, index, errors[st](index, self.ds[t].n_pieces)))
+                r += 1
+            res.append(got)
+        return res
+
     # -- rounds
     def _peer_round(self, always=False):
         """One peer round over the queued joins and fulls (none queued: only when `always`).  The
@@ -522,6 +605,13 @@ class RequestTable:
         joins, self._joins = self._joins, {}
         fulls, self._fulls = self._fulls, {}
         self.slots.events({t: sorted(j.items()) for t, j in joins.items()}, {t: sorted(f) for t, f in fulls.items()})
+        for t, j in joins.items():  # a new connection has sent nothing: its slot's LastPieceSent, with the joins' upload
+            for p in j:
+                at = int(self.batch.peer_off[t]) + p
+                if self.gpu:
+                    self.sent.from_host(np.zeros(1, dtype=np.int64), offset=8 * at)
+                else:
+                    self.sent[at] = 0
         if self.gpu:
             if self.slots.wire.size > self._wire.nbytes:
                 self._wire = D.DeviceBuffer(2 * self.slots.wire.size)
