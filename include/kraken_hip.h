@@ -712,6 +712,97 @@ int krk_serve_round_dev(const krk_request_torrent* torrents_host, const krk_serv
                         uint32_t* n_received_out, uint32_t* n_sent_out, int64_t* sent_dev, uint32_t* n_ok_out,
                         uint64_t* bytes_out, uint64_t* tokens_out, void* stream);
 
+/* ------------------------------------------- receive rounds
+ * The download side's arrival step on the resident rows: Dispatcher.handlePiecePayload
+ * (lib/torrent/scheduler/dispatch/dispatcher.go:532-577) with Torrent.WritePiece
+ * (agentstorage/torrent.go:202-248) for every PiecePayloadMessage queued for a torrent, in arrival
+ * order at one clock instant.  A torrent is its krk_request_torrent, unchanged: only n_pieces,
+ * n_peers (slots), bits_off and peer_off are read.  Its krk_receive_torrent names the blob's length
+ * and piece_length (n_pieces == krk_num_pieces(length, piece_length) or the call is refused), its
+ * n_pieces expected sums, expected[sum_off ..] (the MetaInfo's), and its payloads,
+ * payloads[pay_off .. pay_off + n_pays), n_pays <= KRK_RV_MAX_PAYLOADS.  A payload is a
+ * krk_serve_request: the wire's three int32 fields as they came and `peer`, the slot the message
+ * arrived on, or KRK_PR_NONE for a sender that has left since -- its piece is still judged and
+ * written, attributed to nobody and marked against nobody.  sums[pay_off + r] is the CRC-32 of
+ * payload r's bytes, where krk_piece_sums_dev left it.  With plen(i) as in serve rounds, payload r
+ * takes the FIRST status that applies:
+ *   KRK_RV_CHUNK      offset != 0 or (int64)length != plen(index) (isFullPiece).  MarkInvalid(peer,
+ *                     index) follows: a mark is emitted iff 0 <= index < n_pieces and peer !=
+ *                     KRK_PR_NONE (outside the range no table entry can exist).
+ *   KRK_RV_INDEX      index outside [0, n_pieces), reached only with offset == length == 0
+ *                     (getPiece's "invalid piece index"; a negative index is a status, not a panic).
+ *                     No mark.
+ *   KRK_RV_DUPLICATE  bit index of have was set when the round began, or an earlier payload of this
+ *                     round was OK for this piece (ErrPieceComplete, tested before the sum is
+ *                     looked at: incrementDuplicatePiecesReceived).  No mark.
+ *   KRK_RV_BAD_SUM    sums[pay_off + r] != expected[sum_off + index] ("invalid piece sum").  A mark
+ *                     unless the sender is KRK_PR_NONE.  The piece stays empty: a later payload of
+ *                     the same piece in the same round can still be OK.
+ *   KRK_RV_OK         the piece is written: incrementGoodPiecesReceived,
+ *                     touchLastGoodPieceReceived, the bit set in have, Clear(index).
+ * The live bit is not read: the reference's feed loop dispatches every message that arrived before
+ * the close.  errWritePieceConflict cannot arise: a round is one instant and its writes are serial.
+ * Stored for every payload, at pay_off + r: status_out; file_off_out = piece_length * index if OK,
+ * else 0.  Stored for every torrent: arrived_out[pay_off ..] and arrived_from_out[pay_off ..], the
+ * OK pieces strictly ascending and the slot (or KRK_PR_NONE) each came from -- the `arrived` list of
+ * krk_request_table_round* and the whole input of the AnnouncePiece fan-out (:567-576: every live
+ * slot but the sender; sending stays with the caller) -- n_arrived_out[t] of them;
+ * marks_out[pay_off ..], krk_failed_request with status KRK_PR_INVALID in arrival order -- the
+ * `marks` list of a table round -- n_marks_out[t] of them; of both lists only the first n_*
+ * elements are stored; n_complete_out, the popcount of have after the round; bytes_out =
+ * min(n_complete * piece_length, length) (BytesDownloaded); flags_out: KRK_RV_COMPLETE when
+ * n_complete == n_pieces, KRK_RV_COMPLETED_NOW when that became true in this round (d.complete()'s
+ * trigger; a torrent of 0 pieces is complete and never "now").
+ * Stored for every slot, at peer_off + p: n_good_out and n_duplicate_out.  Where n_good > 0,
+ * received[peer_off + p] = now: `received` is the resident LastGoodPieceReceived array
+ * krk_conn_preempt* reads; its other elements are left alone.
+ * Rows: bit index of have is set for every OK payload.  No other word of bits changes; the peers'
+ * rows are not touched.
+ *
+ * KRK_EINVAL, refused before anything is touched: a peer that is neither < n_peers nor
+ * KRK_PR_NONE, n_pays above the maximum, more than 2^30 slots, a negative length, n_pieces !=
+ * krk_num_pieces(length, piece_length), a piece_length <= 0, an offset of 2^48 or more, a non-zero
+ * reserved field, now < 0, payloads adding up to 2^32 or more, a NULL that is not nullable (bits
+ * with no words, received and the per-slot outputs with no slots, expected with no pieces,
+ * payloads, sums and the per-payload outputs and lists with no payloads are).  The regions the
+ * torrents name in one array must not overlap. */
+#define KRK_RV_MAX_PAYLOADS 4096u
+#define KRK_RV_OK 0u
+#define KRK_RV_CHUNK 1u
+#define KRK_RV_INDEX 2u
+#define KRK_RV_DUPLICATE 3u
+#define KRK_RV_BAD_SUM 4u
+#define KRK_RV_COMPLETE 1u
+#define KRK_RV_COMPLETED_NOW 2u
+typedef struct {
+    int64_t length, piece_length;   /* MetaInfo.Length(), PieceLength() */
+    uint64_t sum_off;               /* first of its n_pieces sums in `expected` */
+    uint64_t pay_off;               /* first payload in `payloads`, `sums`, the per-payload outputs and the lists */
+    uint32_t n_pays;                /* <= KRK_RV_MAX_PAYLOADS */
+    uint32_t reserved;              /* 0 */
+} krk_receive_torrent;              /* parallel to torrents[] */
+/* The whole round of n_torrents torrents on the host.  No device. */
+int krk_receive_round(const krk_request_torrent* torrents, const krk_receive_torrent* receives, uint64_t n_torrents,
+                      uint64_t* bits, const krk_serve_request* payloads, const uint32_t* sums, const uint32_t* expected,
+                      int64_t now, uint32_t* status_out, int64_t* file_off_out, uint32_t* arrived_out,
+                      uint32_t* arrived_from_out, krk_failed_request* marks_out, uint32_t* n_good_out,
+                      uint32_t* n_duplicate_out, int64_t* received, uint32_t* n_arrived_out, uint32_t* n_marks_out,
+                      uint32_t* n_complete_out, uint64_t* bytes_out, uint32_t* flags_out);
+/* The same on the device (receive_round.hip), bit for bit; asynchronous on `stream`: one launch,
+ * one workgroup a torrent.  bits_dev, sums_dev, expected_dev, received_dev and the outputs are
+ * device memory or page-locked host memory (krk_host_alloc), the 64-bit arrays 8-byte and the
+ * others 4-byte aligned: anything else is KRK_EINVAL before anything is launched.  torrents_host,
+ * receives_host and payloads_host are host memory: the payloads are checked as above, and all three
+ * are copied into the library's staging as one block, before the call returns.  n_torrents == 0 is
+ * KRK_OK; KRK_ENODEV without a gfx950 device: there is no fall-back to the host form. */
+int krk_receive_round_dev(const krk_request_torrent* torrents_host, const krk_receive_torrent* receives_host,
+                          uint64_t n_torrents, uint64_t* bits_dev, const krk_serve_request* payloads_host,
+                          const uint32_t* sums_dev, const uint32_t* expected_dev, int64_t now, uint32_t* status_out,
+                          int64_t* file_off_out, uint32_t* arrived_out, uint32_t* arrived_from_out,
+                          krk_failed_request* marks_out, uint32_t* n_good_out, uint32_t* n_duplicate_out,
+                          int64_t* received_dev, uint32_t* n_arrived_out, uint32_t* n_marks_out, uint32_t* n_complete_out,
+                          uint64_t* bytes_out, uint32_t* flags_out, void* stream);
+
 /* ------------------------------------------- announce rounds
  * Whom an announcing peer talks to: the tracker's announce (tracker/trackerserver/announce.go:75-115)
  * for a batch of announces at one clock instant -- peerstore UpdatePeer and GetPeers

@@ -287,6 +287,11 @@ int krk_have_round_geometry(uint64_t* unit_cap, uint64_t* pass_words);
  * requests a torrent brings to a round) -- for the tests that pin krk_serve_round_dev's edges.
  * No device. */
 int krk_serve_round_geometry(uint64_t* chunk, uint64_t* tile);
+/* The shape of receive_round.hip as built (kernel name "receive_round"): the payloads one step of
+ * classify, winners and resolve takes (one a thread) and the keys one workgroup sorts in LDS (the
+ * most payloads a torrent brings to a round) -- for the tests that pin krk_receive_round_dev's
+ * edges.  No device. */
+int krk_receive_round_geometry(uint64_t* chunk, uint64_t* tile);
 /* The shape of the SHA-256 host share as built (offload.cpp): the bytes of one device-to-host copy
  * (a chain longer than that comes down in several), the pinned buffers an offload thread's copy
  * ring has (a chain of more chunks than that wraps it) and those of a resumer

@@ -118,6 +118,11 @@ class krk_serve_torrent(C.Structure):
                 ("n_reqs", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class krk_receive_torrent(C.Structure):
+    _fields_ = [("length", C.c_int64), ("piece_length", C.c_int64), ("sum_off", C.c_uint64), ("pay_off", C.c_uint64),
+                ("n_pays", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class krk_announce_torrent(C.Structure):
     _fields_ = [("n_peers", C.c_uint64), ("n_windows", C.c_uint32), ("cur_row", C.c_uint32), ("n_origins", C.c_uint32),
                 ("reserved", C.c_uint32), ("bits_off", C.c_uint64)]
@@ -241,6 +246,11 @@ def _load() -> C.CDLL:
         "krk_serve_round_dev": (i, [C.POINTER(krk_request_torrent), C.POINTER(krk_serve_torrent), C.c_uint64, vp, vp, vp,
                                     C.c_int64, C.c_uint64] + [vp] * 12),
         "krk_serve_round_geometry": (i, [u64p, u64p]),
+        "krk_receive_round": (i, [C.POINTER(krk_request_torrent), C.POINTER(krk_receive_torrent), C.c_uint64, vp, vp, vp, vp,
+                                  C.c_int64] + [vp] * 13),
+        "krk_receive_round_dev": (i, [C.POINTER(krk_request_torrent), C.POINTER(krk_receive_torrent), C.c_uint64, vp, vp, vp, vp,
+                                      C.c_int64] + [vp] * 14),
+        "krk_receive_round_geometry": (i, [u64p, u64p]),
         "krk_announce_handout": (i, [C.POINTER(krk_announce_torrent), C.c_uint64, u64p, C.POINTER(krk_announce), C.c_uint32,
                                      C.c_uint32, u32p, u32p, u32p]),
         "krk_announce_round": (i, [C.POINTER(krk_announce_torrent), C.c_uint64, u64p, C.POINTER(krk_announce), C.c_uint64,

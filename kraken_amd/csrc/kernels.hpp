@@ -543,6 +543,46 @@ struct SvArrays {
 hipError_t launch_serve_round(const SvTorrent* tors, uint64_t n_tors, const sv::Request* reqs, const uint64_t* live,
                               int64_t now, uint64_t token_size, const SvArrays& a, hipStream_t s);
 
+// One torrent of a receive round (receive_round.hip, receive_round_math.hpp): its `have` row as a
+// request round's, its per-slot outputs from peer_off, its sums, per-payload outputs and lists
+// from pay_off, its expected sums from sum_off, and its staged payloads (sv::Request) from pay_at.
+namespace rv {
+struct Mark;
+}
+struct alignas(16) RvTorrent {
+    uint64_t n_pieces;  // < 2^32
+    uint64_t bits_off;
+    uint64_t peer_off;
+    uint64_t pay_off;
+    uint64_t sum_off;
+    int64_t length, piece_length;
+    uint64_t pay_at;
+    uint32_t n_peers;  // <= 2^30
+    uint32_t n_pays;   // <= kRvTile
+};
+static_assert(sizeof(RvTorrent) == 80, "RvTorrent layout");
+constexpr uint32_t kRvChunk = 256;  // the payloads one step of classify, winners and resolve takes: one a thread
+constexpr uint32_t kRvTile = 4096;  // KRK_RV_MAX_PAYLOADS: the keys one workgroup sorts in LDS
+// The arrays a receive round touches: sums and expected are only read.
+struct RvArrays {
+    uint64_t* bits;
+    const uint32_t *sums, *expected;
+    int64_t* received;
+    uint32_t* status;
+    int64_t* file_off;
+    uint32_t *arrived, *arrived_from;
+    rv::Mark* marks;
+    uint32_t *n_good, *n_duplicate, *n_arrived, *n_marks, *n_complete;
+    uint64_t* bytes;
+    uint32_t* flags;
+};
+// One workgroup a torrent: every per-payload, per-slot and per-torrent output stored, the first
+// n_arrived / n_marks elements of the lists, bit `index` of have set for every written piece,
+// received[peer_off + p] = now where a good piece came.  The payloads are valid (every peer
+// < n_peers or KRK_PR_NONE).
+hipError_t launch_receive_round(const RvTorrent* tors, uint64_t n_tors, const sv::Request* pays, int64_t now, const RvArrays& a,
+                                hipStream_t s);
+
 // ---------------------------------------------------------------- announce rounds
 // One announce round (announce_round.hip, announce_math.hpp): the update launch sets every
 // announcer's bits in window 0 of its torrent (atomic or), the handout launch -- one wave an

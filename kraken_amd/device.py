@@ -8,7 +8,7 @@ import os
 import numpy as np
 
 from ._capi import (check, krk_blob, krk_file_blob, krk_chunk, krk_launch_rec, krk_nodes, krk_planner_rates,
-                    krk_request_torrent, krk_resend_torrent, krk_failed_request, krk_table_torrent, krk_peer_torrent, krk_have_torrent, krk_serve_torrent, krk_announce_torrent, krk_announce, krk_conn_torrent,
+                    krk_request_torrent, krk_resend_torrent, krk_failed_request, krk_table_torrent, krk_peer_torrent, krk_have_torrent, krk_serve_torrent, krk_receive_torrent, krk_announce_torrent, krk_announce, krk_conn_torrent,
                     krk_conn_lists, krk_conn_transition, krk_conn_incoming, lib)
 
 ALIGN = 256  # every blob starts 256-byte aligned in the arena
@@ -1515,6 +1515,126 @@ def serve_round_geometry():
     the most requests a torrent brings to a round)."""
     c, t = C.c_uint64(), C.c_uint64()
     check(lib.krk_serve_round_geometry(C.byref(c), C.byref(t)))
+    return int(c.value), int(t.value)
+
+
+# ------------------------------------------------------------------ receive rounds
+RV_MAX_PAYLOADS = 4096
+RV_OK, RV_CHUNK, RV_INDEX, RV_DUPLICATE, RV_BAD_SUM = 0, 1, 2, 3, 4
+RV_COMPLETE, RV_COMPLETED_NOW = 1, 2
+
+
+class ReceiveBatch:
+    """The piece payloads one receive round judges over a RequestBatch.  .structs is the
+    krk_receive_torrent array parallel to the batch's: the torrents' length and piece_length, their
+    expected sums (`sum_off`: the batch's piece_off unless given) and their payload lists.  plan()
+    packs a round's payloads {torrent: [(slot or PR_NONE, index, offset, length)]}, each list in
+    arrival order, back to back into .payloads (SV_REQUEST); torrent t's payloads, their sums, its
+    per-payload outputs and its two lists start at .pay_off[t]."""
+
+    def __init__(self, batch: RequestBatch, length, piece_length, sum_off=None):
+        k = len(batch)
+        self.batch = batch
+        self.length = np.broadcast_to(np.asarray(length, dtype=np.int64), (k,)).copy()
+        self.piece_length = np.broadcast_to(np.asarray(piece_length, dtype=np.int64), (k,)).copy()
+        self.sum_off = np.asarray(batch.piece_off[:-1] if sum_off is None else sum_off, dtype=np.uint64)
+        self.structs = (krk_receive_torrent * max(k, 1))()
+        self.plan()
+
+    def __len__(self):
+        return len(self.batch)
+
+    def plan(self, payloads=None):
+        payloads = payloads or {}
+        rows, self.pay_off = [], []
+        for t in range(len(self)):
+            mine = list(payloads.get(t, ()))
+            self.pay_off.append(len(rows))
+            self.structs[t] = krk_receive_torrent(int(self.length[t]), int(self.piece_length[t]), int(self.sum_off[t]),
+                                                  len(rows), len(mine), 0)
+            rows.extend(mine)
+        self.payloads = np.array(rows, dtype=SV_REQUEST)
+        k, r, p = len(self), len(rows), self.batch.total_peers
+        self.sizes = (r, r, r, r, r, p, p, k, k, k, k, k)  # elements of ReceiveOutputs.NAMES
+        return self
+
+
+class ReceiveOutputs:
+    """The outputs of receive_round_dev for a planned ReceiveBatch, in device memory or
+    (pinned=True) in page-locked host memory the kernel writes over PCIe: .status and .file_off a
+    payload; .arrived, .arrived_from and .marks (RT_FAILED), the lists, a payload's room each;
+    .n_good and .n_duplicate a peer slot; .n_arrived, .n_marks, .n_complete, .bytes and .flags a
+    torrent.  `margin` elements follow every buffer's last (tests)."""
+    NAMES = ("status", "file_off", "arrived", "arrived_from", "marks", "n_good", "n_duplicate", "n_arrived", "n_marks",
+             "n_complete", "bytes", "flags")
+    DTYPES = (np.uint32, np.int64, np.uint32, np.uint32, RT_FAILED, np.uint32, np.uint32, np.uint32, np.uint32, np.uint32,
+              np.uint64, np.uint32)
+
+    def __init__(self, receive: ReceiveBatch, pinned: bool = False, margin: int = 0):
+        self.pinned, self.sizes = pinned, tuple(k + margin for k in receive.sizes)
+        for name, dt, k in zip(self.NAMES, self.DTYPES, self.sizes):
+            setattr(self, name, PinnedArray((max(k, 1),), dt) if pinned else DeviceBuffer(max(k, 1) * np.dtype(dt).itemsize))
+
+    def fill(self, byte: int):
+        """Every output byte set to `byte` (tests: the call must store exactly what it owns)."""
+        for b in (getattr(self, n) for n in self.NAMES):
+            if self.pinned:
+                b.a.view(np.uint8)[:] = byte
+            else:
+                b.from_host(np.full(b.nbytes, byte, dtype=np.uint8))
+
+    def to_host(self):
+        """The twelve buffers, whole, as numpy arrays in NAMES order, once the call's stream has run."""
+        return tuple(b.a[:k].copy() if self.pinned else b.to_host(dt, k)
+                     for b, dt, k in zip((getattr(self, n) for n in self.NAMES), self.DTYPES, self.sizes))
+
+
+def _receive_args(out, received_ptr):
+    """The thirteen output pointers of a receive call: NAMES with `received` behind n_duplicate."""
+    return out[:7] + [received_ptr] + out[7:]
+
+
+def receive_round(batch: RequestBatch, receive: ReceiveBatch, bits, sums, expected, received, now: int, fill: int = 0,
+                  margin: int = 0):
+    """krk_receive_round: the whole receive round on the host.  bits (uint64, the batch's layout)
+    and received (int64 a peer slot, the LastGoodPieceReceived array) are updated in place; sums:
+    one uint32 a planned payload; expected: the torrents' sums at their sum_off.  Returns
+    ReceiveOutputs.NAMES as numpy arrays, each whole: `margin` elements longer than the plan and
+    holding the byte `fill` wherever the round stored nothing."""
+    for a, t in ((bits, np.uint64), (received, np.int64)):
+        if a.dtype != t or not a.flags.c_contiguous or not a.flags.writeable:
+            raise ValueError(f"receive_round: bits and received are updated in place: a contiguous {t} array each")
+    if bits.size < batch.total_words or received.size < batch.total_peers:
+        raise ValueError("receive_round: bits or received shorter than the batch's layout")
+    sums, expected = (np.ascontiguousarray(a, dtype=np.uint32) for a in (sums, expected))
+    if sums.size < receive.payloads.size:
+        raise ValueError("receive_round: fewer sums than payloads")
+    out = [np.frombuffer(bytearray([fill]) * (max(k + margin, 1) * np.dtype(dt).itemsize), dtype=dt)
+           for dt, k in zip(ReceiveOutputs.DTYPES, receive.sizes)]
+    ptr = lambda a: a.ctypes.data if a.size else None  # noqa: E731
+    check(lib.krk_receive_round(batch.structs, receive.structs, len(batch), ptr(bits), ptr(receive.payloads), ptr(sums),
+                                ptr(expected), int(now), *_receive_args([a.ctypes.data for a in out], ptr(received))))
+    return tuple(a[:k + margin] for a, k in zip(out, receive.sizes))
+
+
+def receive_round_dev(batch: RequestBatch, receive: ReceiveBatch, bits_dev, sums_dev, expected_dev, received_dev, now: int,
+                      out: ReceiveOutputs, stream=None):
+    """krk_receive_round_dev: the receive round in one call on the device, asynchronous on
+    `stream`.  bits_dev and received_dev: DeviceBuffer or PinnedArray in the batch's layout,
+    updated where they lie; sums_dev (where krk_piece_sums_dev left the payloads' sums) and
+    expected_dev likewise, only read.  Returns out, filled once the stream has run the call."""
+    check(lib.krk_receive_round_dev(batch.structs, receive.structs, len(batch), bits_dev.ptr,
+                                    receive.payloads.ctypes.data if receive.payloads.size else None, sums_dev.ptr,
+                                    expected_dev.ptr, int(now),
+                                    *_receive_args([getattr(out, n).ptr for n in out.NAMES], received_dev.ptr), stream))
+    return out
+
+
+def receive_round_geometry():
+    """(the payloads one step of the kernel takes, the keys one workgroup sorts in LDS: the most
+    payloads a torrent brings to a round)."""
+    c, t = C.c_uint64(), C.c_uint64()
+    check(lib.krk_receive_round_geometry(C.byref(c), C.byref(t)))
     return int(c.value), int(t.value)
 
 

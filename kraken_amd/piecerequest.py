@@ -356,7 +356,12 @@ class RequestTable:
 
     The upload side runs on the same rows (``krk_serve_round`` / ``krk_serve_round_dev``):
     ``Requested`` queues a peer's PieceRequestMessage, ``Serve`` answers everything queued in one
-    round, and ``LastPieceSent`` reads the resident array the round keeps."""
+    round, and ``LastPieceSent`` reads the resident array the round keeps.
+
+    So does the download side's arrival step (``krk_receive_round`` / ``krk_receive_round_dev``):
+    ``Received`` queues a peer's PiecePayloadMessage, ``Receive`` judges everything queued against
+    the dispatchers' ``piece_sums`` in one round and queues the arrived pieces and the MarkInvalid
+    pairs for the next table round, and ``LastGoodPieceReceived`` reads the resident array."""
 
     def __init__(self, dispatchers, placement: str = "host", cap: int = D.RT_MAX_ENTRIES, spare_peers: int = 0):
         if placement not in ("host", "gpu"):
@@ -405,6 +410,16 @@ class RequestTable:
             self.sent.from_host(sent)
         else:
             self.sent = sent
+        self._payloads = [[] for _ in self.ds]  # (slot, peerID, index, offset, length, sum), in arrival order
+        self._receive, self._receive_out = None, None  # the ReceiveBatch, and on "gpu" its page-locked outputs
+        self._expected_of = set()  # the torrents whose piece_sums lie in self.expected
+        expected = np.zeros(max(self.batch.total_pieces, 1), dtype=np.uint32)
+        if self.gpu:
+            self.received, self.expected = D.DeviceBuffer(sent.nbytes), D.DeviceBuffer(expected.nbytes)
+            self.received.from_host(sent)  # LastGoodPieceReceived a slot, 0: never
+            self.expected.from_host(expected)
+        else:
+            self.received, self.expected = sent.copy(), expected
 
     def _layout(self, flags, seeds):
         self.batch = D.RequestBatch([d.n_pieces for d in self.ds], [len(ps) for ps in self.peers], flags, seeds)
@@ -595,6 +610,102 @@ class RequestTable:
             res.append(got)
         return res
 
+    # -- the download side: the peers' piece payloads judged on the resident rows
+    def Received(self, t: int, peerID, index: int, offset: int, length: int, sum=None):
+        """The peer's PiecePayloadMessage (handlePiecePayload), queued in arrival order for the next
+        ``Receive``; `sum`: the CRC-32 of its bytes, or None when ``Receive`` is given the sums."""
+        self._payloads[t].append((self.index[t][peerID], peerID, int(index), int(offset), int(length), sum))
+
+    def LastGoodPieceReceived(self, t: int, peerID) -> int:
+        """The clock reading of the peer's last good piece, 0 for none: the resident array."""
+        p = self.index[t][peerID]
+        if p in self._joins.get(t, {}):  # joined since the last round: the slot's element is the peer before it
+            return 0
+        at = int(self.batch.peer_off[t]) + p
+        return int(self.received.to_host(np.int64, 1, offset=8 * at)[0] if self.gpu else self.received[at])
+
+    def Receive(self, sums=None):
+        """One receive round over everything ``Received`` queued, at the managers' clock, and one
+        synchronise -- two on "gpu" when joins are queued, as in ``Serve``.  sums: None for the
+        per-message sums, else one uint32 a queued payload, torrent after torrent and each
+        torrent's in arrival order: a DeviceBuffer on "gpu" (where ``krk_piece_sums_dev`` left
+        them), an array on "host".  The expected sums are the `piece_sums` of every dispatcher with
+        queued payloads, uploaded once and kept.  A payload whose slot another peer has taken since
+        is judged and written all the same, attributed to nobody.  The arrived pieces and the
+        MarkInvalid pairs are queued for the next table round and ``self.have`` follows.  One dict a
+        torrent: "writes", (peerID or None, piece, file_off) in arrival order; "duplicates",
+        (peerID, index); "invalid", (peerID, index, error) with the reference's error texts;
+        "announce", (piece, from peerID or None) ascending by piece -- AnnouncePiece goes to every
+        live peer but that one; "complete", "completed_now" and "bytes" (BytesDownloaded)."""
+        if not self.ds:
+            return []
+        for t, d in enumerate(self.ds):
+            if self._payloads[t] and not all(hasattr(d, a) for a in ("length", "piece_length", "piece_sums")):
+                raise ValueError(f"Receive: torrent {t} has queued payloads and no length / piece_length / piece_sums")
+        if sums is None and any(q[5] is None for qs in self._payloads for q in qs):
+            raise ValueError("Receive: a queued payload has no sum and none were given")
+        queued, self._payloads = self._payloads, [[] for _ in self.ds]
+        self._peer_round()
+        for t, d in enumerate(self.ds):  # the MetaInfo's sums, once a torrent
+            if queued[t] and t not in self._expected_of:
+                mine = np.ascontiguousarray(d.piece_sums, dtype=np.uint32)
+                if mine.size != d.n_pieces:
+                    raise ValueError(f"Receive: torrent {t}: {mine.size} piece sums for {d.n_pieces} pieces")
+                at = int(self.batch.piece_off[t])
+                if self.gpu:
+                    self.expected.from_host(mine, offset=4 * at)
+                else:
+                    self.expected[at:at + mine.size] = mine
+                self._expected_of.add(t)
+        # A torrent without the attributes takes no payload: any consistent pair will do.
+        shape = [(getattr(d, "length", d.n_pieces), getattr(d, "piece_length", 1)) for d in self.ds]
+        if self._receive is None or shape != list(zip(self._receive.length.tolist(), self._receive.piece_length.tolist())):
+            self._receive = D.ReceiveBatch(self.batch, [s[0] for s in shape], [s[1] for s in shape])
+        rec = self._receive.plan({t: [(p if self.peers[t][p] == peerID else D.PR_NONE, i, off, ln) for p, peerID, i, off, ln, _ in qs]
+                                  for t, qs in enumerate(queued) if qs})
+        if sums is None:
+            sums = np.array([q[5] for qs in queued for q in qs], dtype=np.uint32)
+            if self.gpu:
+                host, sums = sums, D.DeviceBuffer(max(sums.nbytes, 4))
+                sums.from_host(host)
+        clocks = {d.manager.clock.Now() for d in self.ds}
+        if len(clocks) != 1:
+            raise ValueError("RequestTable: the dispatchers of a round share one clock reading")
+        now = clocks.pop()
+        if self.gpu:
+            if self._receive_out is None or self._receive_out.sizes[0] < rec.sizes[0]:  # grown on demand, as _wire
+                self._receive_out = D.ReceiveOutputs(rec, pinned=True, margin=rec.sizes[0])
+            D.receive_round_dev(self.batch, rec, self.bits, sums, self.expected, self.received, now, self._receive_out)
+            D.check(D.lib.krk_stream_sync(None))
+            out = [getattr(self._receive_out, n).a for n in D.ReceiveOutputs.NAMES]
+        else:
+            out = D.receive_round(self.batch, rec, self.bits, sums, self.expected, self.received, now)
+        o = dict(zip(D.ReceiveOutputs.NAMES, out))
+        errors = {D.RV_CHUNK: lambda i, n: "reading / writing chunk of piece not supported",
+                  D.RV_INDEX: lambda i, n: f"invalid piece index {i}: num pieces = {n}", D.RV_BAD_SUM: lambda i, n: "invalid piece sum"}
+        res = []
+        for t, qs in enumerate(queued):
+            r, k, m, flags = rec.pay_off[t], int(o["n_arrived"][t]), int(o["n_marks"][t]), int(o["flags"][t])
+            got = {"writes": [], "duplicates": [], "invalid": [], "complete": bool(flags & D.RV_COMPLETE),
+                   "completed_now": bool(flags & D.RV_COMPLETED_NOW), "bytes": int(o["bytes"][t])}
+            name = lambda p: None if p == D.PR_NONE else self.peers[t][p]  # noqa: E731
+            for (p, peerID, index, _, _, _), st, off in zip(qs, o["status"][r:r + len(qs)].tolist(), o["file_off"][r:r + len(qs)].tolist()):
+                if st == D.RV_OK:
+                    got["writes"].append((peerID if self.peers[t][p] == peerID else None, index, off))
+                elif st == D.RV_DUPLICATE:
+                    got["duplicates"].append((peerID, index))
+                else:
+                    got["invalid"].append((peerID, index, errors[st](index, self.ds[t].n_pieces)))
+            pieces = o["arrived"][r:r + k].tolist()
+            got["announce"] = [(i, name(p)) for i, p in zip(pieces, o["arrived_from"][r:r + k].tolist())]
+            if pieces:
+                self.have[t][pieces] = True
+                self._events["arrived"].setdefault(t, set()).update(pieces)
+            if m:
+                self._events["marks"].setdefault(t, []).extend(tuple(int(x) for x in mk) for mk in o["marks"][r:r + m].tolist())
+            res.append(got)
+        return res
+
     # -- rounds
     def _peer_round(self, always=False):
         """One peer round over the queued joins and fulls (none queued: only when `always`).  The
@@ -605,13 +716,14 @@ class RequestTable:
         joins, self._joins = self._joins, {}
         fulls, self._fulls = self._fulls, {}
         self.slots.events({t: sorted(j.items()) for t, j in joins.items()}, {t: sorted(f) for t, f in fulls.items()})
-        for t, j in joins.items():  # a new connection has sent nothing: its slot's LastPieceSent, with the joins' upload
-            for p in j:
+        for t, j in joins.items():  # a new connection has sent and received nothing: its slot's LastPieceSent and
+            for p in j:             # LastGoodPieceReceived, with the joins' upload
                 at = int(self.batch.peer_off[t]) + p
                 if self.gpu:
                     self.sent.from_host(np.zeros(1, dtype=np.int64), offset=8 * at)
+                    self.received.from_host(np.zeros(1, dtype=np.int64), offset=8 * at)
                 else:
-                    self.sent[at] = 0
+                    self.sent[at] = self.received[at] = 0
         if self.gpu:
             if self.slots.wire.size > self._wire.nbytes:
                 self._wire = D.DeviceBuffer(2 * self.slots.wire.size)
